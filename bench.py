@@ -13,6 +13,15 @@ Weak scaling: per-GPU batch is fixed (--batch-per-gpu); the reported value
 is WHOLE-JOB image-pairs/sec (max step time over ranks). Rank 0 prints one
 JSON line. Without a GPU the plumbing config (RAFT-small NCUP, 2 iters,
 128x128 — BASELINE config 1) runs on CPU so the harness stays testable here.
+
+A plain run does only what the headline figure needs: set up, warm up, time
+--steps steps, print the line. --dump-outputs DIR then runs the timed path
+one more time, untimed, and writes what that last step computed as
+DIR/<name>.npy. Inputs and initial weights are seeded, and that step starts
+again from the initial weights, a fresh optimizer state and the schedule's
+first learning rate, so the files are the same from run to run and two
+builds can be compared output for output. Secondary measurements belong behind
+--full; there is none yet.
 """
 
 import argparse
@@ -56,7 +65,63 @@ def parse_args():
     p.add_argument("--torch-profile", default=None,
                    help="write torch.profiler kernel table for steady-state "
                    "steps to this path (after warmup; excludes MIOpen tuning)")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, run the timed path once more "
+                   "from the seeded initial weights and optimizer state and "
+                   "write what it computed (flow predictions, loss, metrics, "
+                   "updated parameters) as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run every secondary measurement. There is none "
+                   "today: a plain run already does only what the headline "
+                   "figure needs, so this changes nothing yet")
+    cli = p.parse_args()
+    if cli.steps < 1:
+        p.error("--steps must be at least 1")
+    if cli.dump_outputs and (cli.torch_profile or cli.profile_steps > 0):
+        p.error("--dump-outputs cannot be combined with --torch-profile or "
+                "--profile-steps, which end before anything is written")
+    return cli
+
+
+# --dump-outputs stays under 64 MB in all: the final prediction and the
+# parameters are written whole where they fit, everything larger as a fixed
+# seeded sample of its elements
+DUMP_WHOLE_MAX = 6 * 2**20   # elements (24 MB of float32)
+DUMP_SAMPLE = 2**16          # elements per sampled array
+DUMP_SEED = 20240
+
+
+def _sample(t, limit):
+    """`t` itself if it has at most `limit` elements, else DUMP_SAMPLE of
+    its elements at seeded indices (the same in every run of that shape)."""
+    if t.numel() <= limit:
+        return t
+    g = torch.Generator().manual_seed(DUMP_SEED)
+    idx = torch.randint(t.numel(), (DUMP_SAMPLE,), generator=g)
+    return t.reshape(-1)[idx.to(t.device)]
+
+
+def _save(out_dir, name, t):
+    np.save(os.path.join(out_dir, name + ".npy"),
+            t.detach().to(device="cpu", dtype=torch.float32).numpy())
+
+
+def dump_outputs(out_dir, captured, model):
+    os.makedirs(out_dir, exist_ok=True)
+    preds = captured["preds"]
+    _save(out_dir, "flow_final", _sample(preds[-1], DUMP_WHOLE_MAX))
+    # every refinement iteration's prediction, one row each, sampled at
+    # shared indices
+    _save(out_dir, "flow_preds", torch.stack(
+        [_sample(p, DUMP_SAMPLE).reshape(-1) for p in preds]))
+    _save(out_dir, "loss", captured["loss"].reshape(1))
+    m = captured["metrics"]
+    np.save(os.path.join(out_dir, "metrics.npy"),
+            np.array([m["epe"], m["1px"], m["3px"], m["5px"]], np.float64))
+    # the parameters after the last optimizer step, in parameters() order
+    _save(out_dir, "params", _sample(torch.cat(
+        [p.detach().reshape(-1).float() for p in model.parameters()]),
+        DUMP_WHOLE_MAX))
 
 
 def main():
@@ -106,10 +171,36 @@ def main():
         coarse, size=(h, w), mode="bilinear", align_corners=False).to(device)
     valid = torch.ones(batch, h, w, device=device)
 
-    def step():
+    captured = {}
+    # The backward pass is not bit-reproducible on the GPU (float atomics),
+    # and bf16 refinement amplifies that over a few optimizer steps. So what
+    # --dump-outputs writes comes from one further, untimed step of the same
+    # path that starts again from the seeded initial weights, a fresh
+    # optimizer state and the schedule's first learning rate: the same in
+    # every run, whatever --steps and --warmup are.
+    params = [p for p in model.parameters()]
+    init_params = ([p.detach().clone() for p in params]
+                   if cli.dump_outputs else None)
+
+    @torch.no_grad()
+    def rewind():
+        # in-place on the parameters themselves, as the optimizer does, so
+        # that their version counters move and cached packed weights refresh
+        torch._foreach_copy_(params, init_params)
+        for st in optimizer.state.values():
+            for v in st.values():
+                if torch.is_tensor(v):
+                    v.zero_()
+        for group, lr in zip(optimizer.param_groups, scheduler.base_lrs):
+            group["lr"] = lr
+
+    def step(capture=False):
         optimizer.zero_grad(set_to_none=True)
         preds = ddp_model(image1, image2, iters=iters)
         loss, metrics = ops.sequence_loss(preds, flow_gt, valid, args.gamma)
+        if capture:
+            captured.update(preds=[p.detach() for p in preds],
+                            loss=loss.detach(), metrics=metrics)
         loss.backward()
         torch.nn.utils.clip_grad_norm_(model.parameters(), 1.0)
         optimizer.step()
@@ -172,6 +263,12 @@ def main():
     ms_per_step = elapsed / cli.steps * 1000.0
     pairs_per_sec = global_batch * cli.steps / elapsed
     peak_gb = (torch.cuda.max_memory_allocated() / 2**30) if on_gpu else None
+
+    if cli.dump_outputs:  # after the clock has stopped; every rank steps
+        rewind()
+        step(capture=rank == 0)
+        if captured:
+            dump_outputs(cli.dump_outputs, captured, model)
 
     if rank == 0:
         print(json.dumps({

@@ -150,6 +150,81 @@ def test_bench_default_invocation(tmp_path):
     assert rec["config"]["global_batch"] == 1
 
 
+def _run_bench(*extra):
+    import subprocess
+    import sys
+
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    return subprocess.run(
+        [sys.executable, os.path.join(repo, "bench.py")] + list(extra),
+        capture_output=True, text=True, timeout=840, cwd=repo)
+
+
+@pytest.mark.timeout(900)
+def test_bench_dump_outputs_and_full(tmp_path):
+    """`--dump-outputs DIR` writes one further step's results as float .npy
+    files under 64 MB in all. That step starts again from the seeded initial
+    weights, optimizer state and learning rate, so a run whose dumped step
+    follows five training steps writes exactly what a run whose dumped step
+    follows one does (it would not if the rewind did nothing), and the final
+    prediction equals a direct call of the seeded model. `--full` is accepted
+    and keeps the JSON contract."""
+    import json
+
+    dumps = []
+    for name, extra in (("a", ["--steps", "3", "--warmup", "2"]),
+                        ("b", ["--steps", "1", "--warmup", "0", "--full"])):
+        out_dir = tmp_path / name
+        res = _run_bench("--dump-outputs", str(out_dir), *extra)
+        assert res.returncode == 0, res.stderr[-2000:]
+        lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        rec = json.loads(lines[0])
+        assert rec["steps"] == int(extra[1]) and rec["ms_per_step"] > 0
+        dumps.append({p.stem: np.load(p) for p in out_dir.glob("*.npy")})
+
+    a, b = dumps
+    assert set(a) == {"flow_final", "flow_preds", "loss", "metrics", "params"}
+    assert sum(v.nbytes for v in a.values()) <= 64 * 2**20
+    assert a["flow_final"].shape == (1, 2, 128, 128)
+    assert a["flow_preds"].shape[0] == 2  # CPU config: 2 refinement iters
+    for k, v in a.items():
+        assert v.dtype in (np.float32, np.float64), k
+        assert np.isfinite(v).all(), k
+        assert np.array_equal(v, b[k]), k
+    # the final prediction is the last row's source
+    assert np.array_equal(a["flow_preds"][-1], a["flow_final"].reshape(-1))
+
+    # a direct call of the model bench.py builds on CPU, on its inputs
+    torch.manual_seed(1234)
+    args = default_ncup_args(model="raft_nc_dbl", small=True,
+                             mixed_precision=False, iters=2, dataset="sintel")
+    model = build_model(args)
+    model.train()
+    model.freeze_bn()
+    g = torch.Generator().manual_seed(4321)
+    image1 = torch.rand(1, 3, 128, 128, generator=g) * 255
+    image2 = torch.rand(1, 3, 128, 128, generator=g) * 255
+    with torch.no_grad():
+        preds = model(image1, image2, iters=2)
+    assert np.array_equal(preds[-1].numpy(), a["flow_final"])
+    # and the dumped parameters are one optimizer step away from these
+    init = torch.cat([p.detach().reshape(-1) for p in model.parameters()])
+    step = np.abs(a["params"] - init.numpy()).max()
+    assert 0 < step < 1e-4  # first learning rate: 1.25e-4 / 25
+
+
+def test_bench_rejects_bad_arguments(tmp_path):
+    """`--steps 0` cannot be timed, and the profiling modes end before
+    anything could be dumped: both are argument errors, not silent no-ops."""
+    res = _run_bench("--steps", "0")
+    assert res.returncode == 2 and "--steps" in res.stderr
+    res = _run_bench("--profile-steps", "1", "--dump-outputs",
+                     str(tmp_path / "d"))
+    assert res.returncode == 2 and "--dump-outputs" in res.stderr
+    assert not (tmp_path / "d").exists()
+
+
 @pytest.mark.timeout(900)
 def test_train_entry_world_size_2(tmp_path):
     """The full train.py CLI under torchrun with 2 CPU ranks (gloo):
