@@ -82,7 +82,7 @@ void flowhip_conv_gemm_fwd_launch(const void* x, const void* x2,
                                   int cpad, int KH, int KW, int padH,
                                   int padW, int osplit, int act, int smode,
                                   hipStream_t stream);
-void flowhip_conv_gemm_wrw_launch(const void* dy, const void* x,
+bool flowhip_conv_gemm_wrw_launch(const void* dy, const void* x,
                                   const void* x2, float* partials, float* dw,
                                   float* dbias,
                                   const void* zpage, long Mtot, int HH,
@@ -90,7 +90,11 @@ void flowhip_conv_gemm_wrw_launch(const void* dy, const void* x,
                                   int ld_x, int ld_x2, int C1,
                                   int Cin, int Cout, int cpad, int KH,
                                   int KW, int padH, int padW, int nchunk,
-                                  hipStream_t stream);
+                                  int algo, hipStream_t stream);
+int flowhip_conv_gemm_wrw_plan(long Mtot, int HH, int WW, int srcH, int srcW,
+                               int sH, int sW, bool has_x2, int C1, int Cout,
+                               int cpad, int KH, int KW, int padH, int padW,
+                               int algo, int nchunk_req, int* nchunk_out);
 void flowhip_instnorm_cl_fwd_launch(const void* x, void* y, float* mean,
                                     float* rstd, float* partials, int N,
                                     int C, long P, float eps, int is_bf16,
@@ -940,7 +944,8 @@ torch::Tensor conv_gemm_fwd(torch::Tensor x, torch::Tensor wpk,
 std::vector<torch::Tensor> conv_gemm_wrw(torch::Tensor dy, torch::Tensor x,
                                          c10::optional<torch::Tensor> x2,
                                          int64_t KH, int64_t KW, int64_t sH,
-                                         int64_t sW, bool want_bias) {
+                                         int64_t sW, bool want_bias,
+                                         int64_t algo, int64_t nchunk_req) {
   int ld_x, ld_x2 = 0;
   cg_check_x(x, ld_x);
   TORCH_CHECK(dy.is_cuda() && dy.scalar_type() == torch::kBFloat16 &&
@@ -962,15 +967,17 @@ std::vector<torch::Tensor> conv_gemm_wrw(torch::Tensor dy, torch::Tensor x,
   const long Mtot = (long)N * OH * OW;
   const int cpad = (int)((Cin + 63) / 64) * 64;
   const int tiles_o = (Cout + 63) / 64;
-  // split M only as much as needed to fill the chip (~2 blocks/CU);
-  // more chunks = more fp32 partial traffic + a longer reduce
-  const int base_tiles = tiles_o * ((cpad + 63) / 64) * (int)(KH * KW);
-  int nchunk = (512 + base_tiles - 1) / base_tiles;
-  if (nchunk < 1) nchunk = 1;
-  if (nchunk > 64) nchunk = 64;  // encoder shapes: few tiles, huge M
-  // never more chunks than 64-row m-tiles
-  const long mtiles = (Mtot + 63) / 64;
-  if (nchunk > mtiles) nchunk = (int)mtiles;
+  // path (generic per-tap | halo-staged) and its split-M chunk count;
+  // the partials buffer below is sized for whichever path runs
+  TORCH_CHECK(algo >= -1 && algo <= 1, "conv_gemm_wrw: algo must be -1, 0, 1");
+  int nchunk = 1;
+  const int path = flowhip_conv_gemm_wrw_plan(
+      Mtot, OH, OW, H, W, (int)sH, (int)sW, x2p != nullptr, C1, Cout, cpad,
+      (int)KH, (int)KW, (int)KH / 2, (int)KW / 2, (int)algo, (int)nchunk_req,
+      &nchunk);
+  TORCH_CHECK(path >= 0,
+              "conv_gemm_wrw: algo=1 (halo) forced on a shape outside its "
+              "envelope (stride 1, same padding, 3x3 / 1x5 / 5x1)");
   // bias partials (nchunk, tiles_o*64) ride at the tail of the same
   // buffer; dbias is written fully by the reduce kernel — no zero-fill
   auto partials = torch::empty(
@@ -984,7 +991,7 @@ std::vector<torch::Tensor> conv_gemm_wrw(torch::Tensor dy, torch::Tensor x,
     dbias = torch::empty({(long)Cout}, x.options().dtype(torch::kFloat32));
   const c10::cuda::CUDAGuard guard(x.device());
   hipStream_t stream = at::cuda::getCurrentCUDAStream().stream();
-  flowhip_conv_gemm_wrw_launch(dy.data_ptr(), x.data_ptr(), x2p,
+  const bool launched = flowhip_conv_gemm_wrw_launch(dy.data_ptr(), x.data_ptr(), x2p,
                                partials.data_ptr<float>(),
                                dw.data_ptr<float>(),
                                want_bias ? dbias.data_ptr<float>() : nullptr,
@@ -992,7 +999,9 @@ std::vector<torch::Tensor> conv_gemm_wrw(torch::Tensor dy, torch::Tensor x,
                                OH, OW, H, W, (int)sH, (int)sW,
                                ld_x, ld_x2, C1, Cin, Cout, cpad, (int)KH,
                                (int)KW, (int)KH / 2, (int)KW / 2, nchunk,
-                               stream);
+                               path, stream);
+  TORCH_CHECK(launched,
+              "conv_gemm_wrw: the halo kernel refused a planned shape");
   return {dw, dbias};
 }
 
@@ -1308,10 +1317,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("smode") = 0, py::arg("outH") = 0, py::arg("outW") = 0);
   m.def("conv_gemm_wrw", &conv_gemm_wrw,
         "implicit-GEMM conv weight gradient (split-M + reduce); returns "
-        "[dw, dbias] — dbias undefined unless want_bias",
+        "[dw, dbias] — dbias undefined unless want_bias. algo: -1 auto, "
+        "0 generic per-tap kernel, 1 halo-staged kernel; nchunk: 0 auto",
         py::arg("dy"), py::arg("x"), py::arg("x2"), py::arg("KH"),
         py::arg("KW"), py::arg("sH") = 1, py::arg("sW") = 1,
-        py::arg("want_bias") = false);
+        py::arg("want_bias") = false, py::arg("algo") = -1,
+        py::arg("nchunk") = 0);
   m.def("instnorm_cl_fwd", &instnorm_cl_fwd,
         "channels-last InstanceNorm2d forward (y, mean, rstd)");
   m.def("instnorm_cl_bwd", &instnorm_cl_bwd,

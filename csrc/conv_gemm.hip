@@ -29,7 +29,13 @@
 //   bwd-data:  SAME kernel with w' = flip(w).T packed as [kyx][ci][co]
 //   wrw:       dW[o, kyx, c] = sum_m dy[m, o] * x[m*s+off, c]
 //              (split-M partials + small reduce; MFMA over the m axis with
-//              LDS-transposed fragment reads)
+//              LDS-transposed fragment reads). Two partials kernels share
+//              the partials layout, the bias-gradient contract and the
+//              reduce: the generic per-tap kernel below (any stride, any
+//              tap geometry) and the halo-staged kernel of
+//              conv_wrw_halo.hip (stride-1 same-padding 3x3 / 1x5 / 5x1),
+//              which stages dy and one x halo tile once for all taps.
+//              flowhip_conv_gemm_wrw_plan picks the path.
 //
 // Weight packing (host side, cached per weight version):
 //   wpk[kyx][o][c_pad]  (c_pad = roundup(Cin, 64), zero-filled)
@@ -37,6 +43,7 @@
 // the per-lane glds source address.
 
 #include "common.h"
+#include "conv_wrw_halo_maps.h"
 
 #define CG_BM 64
 #define CG_BN 64
@@ -662,14 +669,84 @@ void flowhip_conv_gemm_fwd_launch(const void* x, const void* x2,
                         offW, osplit, act, smode, stream);
 }
 
-void flowhip_conv_gemm_wrw_launch(const void* dy, const void* x,
+bool flowhip_conv_wrw_halo_launch(const void* dy, const void* x,
+                                  const void* x2, float* partials,
+                                  float* biasp, const void* zpage, int N,
+                                  int H, int W, int ld_x, int ld_x2, int C1,
+                                  int Cin, int Cout, int cpad, int KH, int KW,
+                                  int nchunk, hipStream_t stream);
+
+// Chooses the weight-gradient path and its split-M chunk count; the caller
+// sizes the partials buffer (nchunk * KYX * tiles_o*64 * cpad weight
+// partials + nchunk * tiles_o*64 bias partials) from the result.
+//   algo: -1 auto, 0 generic per-tap kernel, 1 halo-staged kernel
+//         (conv_wrw_halo.hip). Returns the path taken (0 | 1), or -1 when
+//         algo == 1 was forced on a shape outside the halo envelope.
+//   nchunk_req: 0 = the path's own choice, else forced (clamped).
+int flowhip_conv_gemm_wrw_plan(long Mtot, int HH, int WW, int srcH, int srcW,
+                               int sH, int sW, bool has_x2, int C1, int Cout,
+                               int cpad, int KH, int KW, int padH, int padW,
+                               int algo, int nchunk_req, int* nchunk_out) {
+  const int tiles_o = fh_cdiv(Cout, 64);
+  const int tiles_c = fh_cdiv(cpad, 64);
+  // halo envelope: stride 1, same padding, the three tap geometries the
+  // forward halo kernel covers
+  const bool eligible =
+      sH == 1 && sW == 1 && srcH == HH && srcW == WW && padH == KH / 2 &&
+      padW == KW / 2 &&
+      ((KH == 3 && KW == 3) || (KH == 1 && KW == 5) ||
+       (KH == 5 && KW == 1)) &&
+      cpad % 64 == 0 && Cout % 8 == 0 && (!has_x2 || C1 % 64 == 0) &&
+      Mtot <= 0x7fffffffL;
+  if (algo == 1 && !eligible) return -1;
+  const long ptiles = eligible ? (Mtot / ((long)HH * WW)) *
+                                     fh_cdiv(HH, WH_TH) * fh_cdiv(WW, WH_TW)
+                               : 0;
+  // auto follows tools/bench_wrw.py (profiles/README.md round 3): the halo
+  // kernel wins where one staged tile pair feeds enough output tiles or a
+  // long pixel walk — 8+ output tiles (update block: 256->192, 256->126,
+  // 128->256 3x3 and the 384-channel 1x5 / 5x1 GRU convs, 6-22% faster),
+  // or 4+ output tiles over 672+ pixel tiles (96-channel encoder stage,
+  // 20-39%). It measured SLOWER, and stays on the generic kernel, for
+  // 128->64 and 256->2 at 56x128 (2-4 output tiles: too few workgroups
+  // for a kernel that owns its CU) and for the 64- and 128-channel
+  // encoder stages. The rule is fitted to those measured classes only: the
+  // 672 threshold is the batch-3 96-channel encoder shape, the smallest
+  // 4-tile class that won; nothing between the measured points is known.
+  const int tiles = tiles_o * tiles_c;
+  const bool wins = tiles >= 8 || (tiles >= 4 && ptiles >= 672);
+  const bool halo = eligible && (algo == 1 || (algo == -1 && wins));
+  if (halo) {
+    long n = nchunk_req > 0 ? nchunk_req : wh_nchunk(ptiles, tiles_o * tiles_c);
+    if (n > ptiles) n = ptiles;
+    if (n > 4096) n = 4096;
+    *nchunk_out = (int)n;
+    return 1;
+  }
+  // generic: split M only as much as needed to fill the chip (~2 blocks
+  // per CU); more chunks = more fp32 partial traffic + a longer reduce
+  const int base_tiles = tiles_o * tiles_c * KH * KW;
+  int nchunk = nchunk_req > 0 ? nchunk_req
+                              : (512 + base_tiles - 1) / base_tiles;
+  if (nchunk < 1) nchunk = 1;
+  if (nchunk > 64) nchunk = 64;  // encoder shapes: few tiles, huge M
+  // never more chunks than 64-row m-tiles
+  const long mtiles = (Mtot + 63) / 64;
+  if (nchunk > mtiles) nchunk = (int)mtiles;
+  *nchunk_out = nchunk;
+  return 0;
+}
+
+// algo / nchunk: as returned by flowhip_conv_gemm_wrw_plan. Returns false
+// (nothing launched) if the halo kernel refuses a planned shape.
+bool flowhip_conv_gemm_wrw_launch(const void* dy, const void* x,
                                   const void* x2, float* partials, float* dw,
                                   float* dbias, const void* zpage, long Mtot,
                                   int HH,
                                   int WW, int srcH, int srcW, int sH, int sW,
                                   int ld_x, int ld_x2, int C1, int Cin,
                                   int Cout, int cpad, int KH, int KW,
-                                  int padH, int padW, int nchunk,
+                                  int padH, int padW, int nchunk, int algo,
                                   hipStream_t stream) {
   const int tiles_o = fh_cdiv(Cout, 64);
   const int tiles_c = fh_cdiv(cpad, 64);
@@ -678,24 +755,37 @@ void flowhip_conv_gemm_wrw_launch(const void* dy, const void* x,
       ? partials + (long)nchunk * KH * KW * tiles_o * 64 * cpad
       : nullptr;
   dim3 block(CG_THREADS);
-  // (a KW=3 tap-sharing wrw variant was measured SLOWER despite 3x less
-  // operand re-read: the 4-image LDS set halves occupancy and the
-  // encoder working sets are largely L3-resident, so the re-reads were
-  // cheaper than modeled — within-box A/B 41.0 vs 42.65 pairs/s)
-  dim3 grid(tiles_o * tiles_c, KH * KW, nchunk);
-  hipLaunchKernelGGL(conv_gemm_wrw_kernel, grid, block, 0, stream,
-                     (const __bf16*)dy, (const __bf16*)x,
-                     (const __bf16*)x2, partials, biasp,
-                     (const __bf16*)zpage,
-                     Mtot, HH, WW, srcH, srcW, sH, sW, ld_x, ld_x2, C1,
-                     Cin, Cout, cpad, KH, KW, padH, padW, tiles_o, tiles_c,
-                     nchunk);
+  if (algo == 1) {
+    // halo-staged kernel: one staging of dy and of an x halo tile serves
+    // all KH*KW taps; same partials layout, same reduce
+    const int N = (int)(Mtot / ((long)HH * WW));
+    if (!flowhip_conv_wrw_halo_launch(dy, x, x2, partials, biasp, zpage, N,
+                                      HH, WW, ld_x, ld_x2, C1, Cin, Cout,
+                                      cpad, KH, KW, nchunk, stream))
+      // the plan admitted a shape the kernel refuses: a bug the caller
+      // reports, not a fall-back case
+      return false;
+  } else {
+    // (a KW=3 tap-sharing wrw variant that shared only dy and kept one x
+    // image per tap was measured SLOWER despite 3x less operand re-read:
+    // the 4-image LDS set halves occupancy — within-box A/B 41.0 vs 42.65
+    // pairs/s. The halo kernel above keeps ONE x image.)
+    dim3 grid(tiles_o * tiles_c, KH * KW, nchunk);
+    hipLaunchKernelGGL(conv_gemm_wrw_kernel, grid, block, 0, stream,
+                       (const __bf16*)dy, (const __bf16*)x,
+                       (const __bf16*)x2, partials, biasp,
+                       (const __bf16*)zpage,
+                       Mtot, HH, WW, srcH, srcW, sH, sW, ld_x, ld_x2, C1,
+                       Cin, Cout, cpad, KH, KW, padH, padW, tiles_o, tiles_c,
+                       nchunk);
+  }
   const long total = (long)Cout * Cin * KH * KW;
   long rblocks = (total + CG_THREADS - 1) / CG_THREADS;
   if (rblocks > 4096) rblocks = 4096;
   hipLaunchKernelGGL(conv_gemm_wrw_reduce_kernel, dim3((int)rblocks), block,
                      0, stream, partials, dw, biasp, dbias, nchunk, KH * KW,
                      tiles_o * 64, cpad, Cout, Cin);
+  return true;
 }
 
 // ---------------------------------------------------------------------------
