@@ -17,6 +17,14 @@ void flowhip_corr_lookup_fwd_launch(const void* const* levels, const int* Hs,
                                     void* out, int BP, int P,
                                     int L, int radius, int cl, int ldc,
                                     int is_bf16, hipStream_t stream);
+bool flowhip_alt_corr_supported(int D, int radius, int L);
+bool flowhip_alt_corr_lookup_fwd_launch(const void* f1,
+                                        const void* const* levels,
+                                        const int* Hs, const int* Ws,
+                                        const float* coords, void* out,
+                                        int BP, int P, int D, int L,
+                                        int radius, int cl, int ldc,
+                                        int out_bf16, hipStream_t stream);
 void flowhip_corr_lookup_bwd_launch(const void* gout, const float* coords,
                                     void* const* glevels, const int* Hs,
                                     const int* Ws, int BP, int P,
@@ -266,6 +274,78 @@ torch::Tensor corr_lookup_fwd(std::vector<torch::Tensor> pyramid,
   flowhip_corr_lookup_fwd_launch(
       ptrs, Hs, Ws, coords.data_ptr<float>(), full.data_ptr(), B * P, P, L,
       (int)radius, channels_last ? 1 : 0, (int)C8, bf ? 1 : 0, stream);
+  return out;
+}
+
+bool alt_corr_supported(int64_t D, int64_t radius, int64_t L) {
+  return flowhip_alt_corr_supported((int)D, (int)radius, (int)L);
+}
+
+// On-demand window lookup (alt_corr.hip): f1 (B,P,D) bf16 rows, levels =
+// pooled f2 (B,Hl,Wl,D) bf16 channels-last. The emitted tensor (dtype,
+// layout, 8-aligned channel stride) is the one corr_lookup_fwd emits.
+torch::Tensor alt_corr_lookup_fwd(torch::Tensor f1,
+                                  std::vector<torch::Tensor> levels,
+                                  torch::Tensor coords, int64_t radius,
+                                  bool channels_last, bool out_bf16) {
+  TORCH_CHECK(!levels.empty() && levels.size() <= 4,
+              "alt_corr_lookup: 1..4 levels");
+  TORCH_CHECK(coords.is_cuda() && coords.dtype() == torch::kFloat32 &&
+              coords.is_contiguous() && coords.dim() == 4 &&
+              coords.size(1) == 2,
+              "alt_corr_lookup: coords must be contiguous fp32 (B,2,H,W)");
+  const int B = coords.size(0), H = coords.size(2), W = coords.size(3);
+  const int P = H * W;
+  const int L = (int)levels.size();
+  const int K = 2 * (int)radius + 1;
+  TORCH_CHECK(f1.is_cuda() && f1.dtype() == torch::kBFloat16 &&
+              f1.is_contiguous() && f1.dim() == 3,
+              "alt_corr_lookup: f1 must be contiguous bf16 (B,P,D)");
+  TORCH_CHECK(f1.size(0) == B && f1.size(1) == P,
+              "alt_corr_lookup: f1 / coords shape mismatch");
+  const int D = f1.size(2);
+  TORCH_CHECK(flowhip_alt_corr_supported(D, (int)radius, L),
+              "alt_corr_lookup: unsupported D / radius / levels");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(f1.data_ptr()) & 15) == 0,
+              "alt_corr_lookup: f1 must be 16-byte aligned");
+
+  const void* ptrs[4] = {nullptr, nullptr, nullptr, nullptr};
+  int Hs[4] = {0, 0, 0, 0}, Ws[4] = {0, 0, 0, 0};
+  for (int l = 0; l < L; ++l) {
+    auto& lvl = levels[l];
+    TORCH_CHECK(lvl.is_cuda() && lvl.is_contiguous() &&
+                lvl.dtype() == torch::kBFloat16 && lvl.dim() == 4,
+                "alt_corr_lookup: contiguous bf16 (B,Hl,Wl,D) levels required");
+    TORCH_CHECK(lvl.size(0) == B && lvl.size(3) == D,
+                "alt_corr_lookup: level batch / channel mismatch");
+    TORCH_CHECK(lvl.size(1) >= 1 && lvl.size(2) >= 1,
+                "alt_corr_lookup: empty level");
+    TORCH_CHECK((reinterpret_cast<uintptr_t>(lvl.data_ptr()) & 15) == 0,
+                "alt_corr_lookup: levels must be 16-byte aligned");
+    ptrs[l] = lvl.data_ptr();
+    Hs[l] = lvl.size(1);
+    Ws[l] = lvl.size(2);
+  }
+  TORCH_CHECK(Hs[0] == H && Ws[0] == W,
+              "alt_corr_lookup: level 0 must match the coords grid");
+
+  const auto odt = out_bf16 ? torch::kBFloat16 : torch::kFloat32;
+  const long C = (long)L * K * K;
+  const long C8 = channels_last ? (C + 7) / 8 * 8 : C;
+  auto full = channels_last
+                  ? torch::empty({B, C8, H, W},
+                                 coords.options().dtype(odt)
+                                     .memory_format(torch::MemoryFormat::ChannelsLast))
+                  : torch::empty({B, C, H, W},
+                                 coords.options().dtype(odt));
+  auto out = (C8 != C) ? full.narrow(1, 0, C) : full;
+  const c10::cuda::CUDAGuard guard(coords.device());
+  hipStream_t stream = at::cuda::getCurrentCUDAStream().stream();
+  bool ok = flowhip_alt_corr_lookup_fwd_launch(
+      f1.data_ptr(), ptrs, Hs, Ws, coords.data_ptr<float>(), full.data_ptr(),
+      B * P, P, D, L, (int)radius, channels_last ? 1 : 0, (int)C8,
+      out_bf16 ? 1 : 0, stream);
+  TORCH_CHECK(ok, "alt_corr_lookup: unsupported configuration");
   return out;
 }
 
@@ -1260,6 +1340,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("out_bf16") = false);
   m.def("corr_lookup_fwd", &corr_lookup_fwd,
         "fused multi-level correlation window lookup (fp32/bf16 levels)");
+  m.def("alt_corr_lookup_fwd", &alt_corr_lookup_fwd,
+        "on-demand correlation window lookup from feature maps");
+  m.def("alt_corr_supported", &alt_corr_supported,
+        "alt_corr_lookup_fwd envelope (D, radius, levels)");
   m.def("corr_lookup_bwd", &corr_lookup_bwd,
         "backward of corr_lookup_fwd (pyramid grads; accumulates into "
         "`prev` when the pyramid is iteration-chained)",

@@ -70,7 +70,7 @@ def demo(args):
             viz(image1, flow_up, os.path.join(args.out, "flow_%04d.png" % i))
 
 
-if __name__ == "__main__":
+def build_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument("--model", help="checkpoint path")
     parser.add_argument("--arch", default="raft", help="model architecture")
@@ -78,5 +78,12 @@ if __name__ == "__main__":
     parser.add_argument("--out", default="demo_out")
     parser.add_argument("--small", action="store_true")
     parser.add_argument("--mixed_precision", action="store_true")
+    parser.add_argument("--alternate_corr", action="store_true",
+                        help="on-demand correlation lookup (no all-pairs "
+                        "volume; for frames larger than memory allows)")
     add_ncup_module_flags(parser)
-    demo(parser.parse_args())
+    return parser
+
+
+if __name__ == "__main__":
+    demo(build_parser().parse_args())

@@ -212,6 +212,9 @@ def build_train_parser(argv=None):
     parser.add_argument("--resume_full", default=None,
                         help="resume full train state (model/opt/sched/step)")
     parser.add_argument("--seed", type=int, default=1234)
+    parser.add_argument("--alternate_corr", action="store_true",
+                        help="on-demand correlation lookup (no all-pairs "
+                        "volume; memory-bounded, for large frames)")
     parser.add_argument("--profile_dir", default=None,
                         help="rank-0 torch.profiler capture: wait 1 / warmup "
                         "2 / active 3 steps, chrome trace + op table written "
@@ -236,6 +239,9 @@ def build_eval_parser(argv=None):
     parser.add_argument("--compressed_ft", action="store_true")
     parser.add_argument("--iters", type=int, default=None,
                         help="override per-dataset default refinement iters")
+    parser.add_argument("--alternate_corr", action="store_true",
+                        help="on-demand correlation lookup (no all-pairs "
+                        "volume; memory-bounded, for large frames)")
 
     add_ncup_module_flags(parser, argv=argv)
     return parser
@@ -255,7 +261,7 @@ def default_ncup_args(**overrides):
     construction (tests, bench)."""
     ns = argparse.Namespace(
         model="raft_nc_dbl", small=False, dropout=0.0, mixed_precision=False,
-        dataset="sintel", gamma=0.85, iters=12,
+        dataset="sintel", gamma=0.85, iters=12, alternate_corr=False,
         load_pretrained=None, freeze_raft=False,
         final_upsampling="NConvUpsampler",
         final_upsampling_scale=4,

@@ -9,7 +9,7 @@ volume runs in bf16-in/fp32-accumulate MFMA on GPU.
 import torch
 import torch.nn as nn
 
-from ..nn.corr import CorrBlock
+from ..nn.corr import AlternateCorrBlock, CorrBlock
 from ..nn.extractor import BasicEncoder, SmallEncoder
 from ..nn.update import BasicUpdateBlock, SmallUpdateBlock
 from ..utils.amp import autocast_ctx, autocast_off_ctx
@@ -74,7 +74,12 @@ class RAFT(nn.Module):
         with autocast_off_ctx(image1):
             fmap1 = fmap1.float()
             fmap2 = fmap2.float()
-            corr_fn = CorrBlock(fmap1, fmap2, radius=self.args.corr_radius)
+            if getattr(self.args, "alternate_corr", False):
+                corr_fn = AlternateCorrBlock(fmap1, fmap2,
+                                             radius=self.args.corr_radius)
+            else:
+                corr_fn = CorrBlock(fmap1, fmap2,
+                                    radius=self.args.corr_radius)
 
         cnet = self.cnet(image1)
         net, inp = torch.split(cnet, [self.hidden_dim, self.context_dim], dim=1)

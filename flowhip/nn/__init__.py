@@ -1,4 +1,4 @@
-from .corr import CorrBlock
+from .corr import AlternateCorrBlock, CorrBlock
 from .extractor import BasicEncoder, BottleneckBlock, ResidualBlock, SmallEncoder
 from .update import (
     BasicMotionEncoder,
@@ -11,6 +11,7 @@ from .update import (
 )
 
 __all__ = [
+    "AlternateCorrBlock",
     "CorrBlock",
     "BasicEncoder", "SmallEncoder", "ResidualBlock", "BottleneckBlock",
     "FlowHead", "ConvGRU", "SepConvGRU", "SmallMotionEncoder",

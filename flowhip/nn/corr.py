@@ -9,6 +9,7 @@ loop hipGraph-capturable.
 """
 
 from .. import ops
+from ..ops.functional import AltOperandLevels, alt_f1_rows
 
 
 class CorrBlock:
@@ -22,3 +23,26 @@ class CorrBlock:
         out, self.corr_pyramid = ops.corr_lookup_chained(
             self.corr_pyramid, coords, self.radius)
         return out
+
+
+class AlternateCorrBlock:
+    """On-demand correlation (upstream RAFT's `--alternate_corr`): same call
+    signature and output as CorrBlock, but the window correlations are
+    computed from the two feature maps at every lookup, so nothing larger
+    than O(P*D) is kept — no all-pairs volume, no pyramid of it. Per pair it
+    builds the pooled f2 levels (and, on GPU, the bf16 f1 rows) once."""
+
+    def __init__(self, fmap1, fmap2, num_levels=4, radius=4):
+        self.num_levels = num_levels
+        self.radius = radius
+        self.fmap1 = fmap1
+        self.fmap2 = fmap2
+        self.levels = ops.alt_corr_pyramid(fmap2, num_levels)
+        self.f1_rows = None
+        if isinstance(self.levels, AltOperandLevels):
+            self.f1_rows = alt_f1_rows(fmap1)
+
+    def __call__(self, coords):
+        return ops.alt_corr_lookup(self.fmap1, self.levels, coords,
+                                   self.radius, fmap2=self.fmap2,
+                                   f1_rows=self.f1_rows)

@@ -8,6 +8,8 @@ SURVEY.md §2.2 kernel inventory):
   corr_volume(fmap1, fmap2)            kernel #1  (MFMA batched GEMM)
   corr_pyramid(corr, num_levels)       kernel #2  (avg-pool pyramid)
   corr_lookup(pyramid, coords, r)      kernel #3  (4-level 81-tap gather+lerp)
+  alt_corr_pyramid(fmap2, num_levels)  pooled f2 levels for the on-demand mode
+  alt_corr_lookup(f1, levels, coords, r)  on-demand window lookup, no volume
   nconv2d(...)                         kernel #6  (fused normalized conv)
   conf_pool(data, conf)                kernel #7  (confidence-based pooling)
   zero_inject(x, sh, sw)               kernel #8  (sparse injection scatter)
@@ -83,6 +85,49 @@ def corr_lookup_chained(pyramid, coords, radius):
         res = CorrLookupFn.apply(coords, radius, *pyramid)
         return res[0], list(res[1:])
     return torch_ref.corr_lookup(pyramid, coords, radius), pyramid
+
+
+def alt_corr_pyramid(fmap2, num_levels=4):
+    """Pooled second-feature-map pyramid for the on-demand lookup.
+
+    HIP path: the kernel's operand form — (B, Hl, Wl, D) bf16 channels-last
+    levels, detached (gradients reach fmap2 through `alt_corr_lookup`'s
+    `fmap2` argument). Outside the kernel's envelope (D % 8, D <= 512,
+    1..4 levels) and on CPU: the differentiable fp32 (B, D, Hl, Wl) levels
+    of `torch_ref.alt_corr_pyramid`, which select the torch lookup."""
+    if _ext.use_hip(fmap2):
+        # the radius is checked at lookup time; 4 stands in for it here
+        if _ext.ext().alt_corr_supported(fmap2.shape[1], 4, num_levels):
+            from .functional import alt_f2_levels
+            return alt_f2_levels(fmap2, num_levels)
+        import warnings
+        warnings.warn(
+            f"alt_corr_pyramid: D={fmap2.shape[1]}, {num_levels} levels is "
+            "outside the on-demand lookup kernel's envelope; using the "
+            "chunked torch path")
+    return torch_ref.alt_corr_pyramid(fmap2, num_levels)
+
+
+def alt_corr_lookup(fmap1, fmap2_levels, coords, radius, fmap2=None,
+                    f1_rows=None):
+    """Correlation window lookup without the all-pairs volume; same output
+    (values, dtype, layout) as `corr_lookup` on the pyramid of
+    `corr_volume(fmap1, fmap2)`.
+
+    `fmap2_levels` comes from `alt_corr_pyramid`. On the HIP path `fmap2`
+    is the map the levels were built from — required only for its gradient;
+    `f1_rows` optionally passes a cached `functional.alt_f1_rows(fmap1)`."""
+    from .functional import AltOperandLevels
+    if isinstance(fmap2_levels, AltOperandLevels):
+        if radius in (3, 4) and _ext.use_hip(coords):
+            from .functional import AltCorrLookupFn, alt_f1_rows
+            if f1_rows is None:
+                f1_rows = alt_f1_rows(fmap1)
+            return AltCorrLookupFn.apply(coords, radius, fmap1, fmap2,
+                                         f1_rows, *fmap2_levels)
+        # other radii: torch path on the rounded operands
+        fmap2_levels = [x.permute(0, 3, 1, 2).float() for x in fmap2_levels]
+    return torch_ref.alt_corr_lookup(fmap1, fmap2_levels, coords, radius)
 
 
 def nconv2d(data, conf, weight, bias=None, stride=1, padding=0, dilation=1,

@@ -181,3 +181,120 @@ class CorrPyramidFn(torch.autograd.Function):
         gs = [g.contiguous() if g is not None else None for g in grads]
         dcorr = _ext.ext().corr_pyramid_bwd(gs, ctx.corr_shape)
         return dcorr, None
+
+
+# budget of one recomputed correlation slab in the chunked backward
+# (elements; fp32 -> 64 MiB for level 0, ~1/3 more for the coarser levels)
+_ALT_BWD_SLAB = 1 << 24
+
+
+def alt_f1_rows(fmap1):
+    """(B, D, H, W) feature map -> (B, P, D) bf16 rows, rounded once: the
+    `f1` operand of the on-demand lookup kernel. Channels-last memory already
+    is this layout."""
+    B, D, H, W = fmap1.shape
+    with torch.no_grad():
+        return fmap1.detach().permute(0, 2, 3, 1).reshape(B, H * W, D).to(
+            torch.bfloat16).contiguous()
+
+
+class AltOperandLevels(list):
+    """List of pooled f2 levels in the lookup kernel's operand form
+    ((B, Hl, Wl, D) bf16); the type tells `ops.alt_corr_lookup` apart from
+    the torch path's (B, D, Hl, Wl) levels."""
+
+
+def alt_f2_levels(fmap2, num_levels):
+    """Pooled (B, Hl, Wl, D) bf16 channels-last levels of the second feature
+    map: floor-mode 2x2 averaging in fp32, each level rounded to bf16 once.
+    Built once per image pair, not on the hot path."""
+    from . import torch_ref
+    with torch.no_grad():
+        lv = torch_ref.alt_corr_pyramid(fmap2.detach().float(), num_levels)
+        return AltOperandLevels(
+            x.permute(0, 2, 3, 1).to(torch.bfloat16).contiguous() for x in lv)
+
+
+class AltCorrLookupFn(torch.autograd.Function):
+    """On-demand correlation window lookup (`--alternate_corr`): what
+    CorrLookupFn gathers out of the all-pairs pyramid, computed from the
+    feature maps by `alt_corr_lookup_fwd` with nothing of size P^2 alive.
+
+    forward(coords, radius, fmap1, fmap2, f1_rows, *levels): `f1_rows` and
+    `levels` are the bf16 kernel operands (`alt_f1_rows`, `alt_f2_levels`),
+    built once per pair; `fmap1` / `fmap2` (B, D, H, W) only carry the
+    autograd graph and may be None when no gradient is wanted. coords must
+    be detached, as for CorrLookupFn. Only coords, f1_rows and the levels
+    are saved.
+
+    backward returns gradients for fmap1 and fmap2. There is no HIP backward
+    kernel: the window correlations are recomputed with torch ops in chunks
+    of target pixels (one (chunk, Hl, Wl) slab per level, at most
+    `_ALT_BWD_SLAB` elements at level 0) and differentiated chunk by chunk,
+    so the backward never allocates more than that fixed slab plus O(P*D)
+    accumulators. Each lookup of the iteration loop repeats the recompute:
+    training in this mode is memory-bounded, not tuned (cost on file in
+    profiles/README.md).
+    """
+
+    @staticmethod
+    def forward(ctx, coords, radius, fmap1, fmap2, f1_rows, *levels):
+        from ..utils.layout import channels_last_enabled, corr_bf16_enabled
+        assert not coords.requires_grad, (
+            "alt_corr_lookup: coords must be detached (reference contract)")
+        coords_c = coords.contiguous()
+        cl = channels_last_enabled()
+        out = _ext.ext().alt_corr_lookup_fwd(
+            f1_rows, list(levels), coords_c, int(radius), cl,
+            corr_bf16_enabled())
+        ctx.save_for_backward(coords_c, f1_rows, *levels)
+        ctx.radius = int(radius)
+        ctx.fmap_shape = None if fmap1 is None else tuple(fmap1.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        from . import torch_ref
+        coords, f1_rows, *levels = ctx.saved_tensors
+        B, P, D = f1_rows.shape
+        need1, need2 = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        if not (need1 or need2):
+            return (None,) * (5 + len(levels))
+        H, W = coords.shape[-2:]
+        g = grad.float().reshape(B, -1, P).transpose(1, 2)      # (B, P, C)
+        xy = coords.reshape(B, 2, P).transpose(1, 2)            # (B, P, 2)
+        chunk = max(1, min(P, _ALT_BWD_SLAB // P))
+        gf1 = torch.zeros(B, P, D, device=grad.device, dtype=torch.float32)
+        glv = [torch.zeros(x.shape, device=grad.device, dtype=torch.float32)
+               for x in levels]
+        with torch.enable_grad():
+            for b in range(B):
+                # (D, Hl, Wl) fp32 views of the saved bf16 operands
+                lv = [x[b].float().permute(2, 0, 1).requires_grad_(need2)
+                      for x in levels]
+                for s in range(0, P, chunk):
+                    rows = f1_rows[b, s:s + chunk].float().requires_grad_(
+                        need1)
+                    o = torch_ref.alt_corr_chunk(rows, lv, xy[b, s:s + chunk],
+                                                 ctx.radius)
+                    wanted = ([rows] if need1 else []) + (lv if need2 else [])
+                    gs = torch.autograd.grad(o, wanted, g[b, s:s + chunk])
+                    if need1:
+                        gf1[b, s:s + chunk] = gs[0]
+                        gs = gs[1:]
+                    if need2:
+                        for acc, gl in zip(glv, gs):
+                            acc[b] += gl.permute(1, 2, 0)
+        df1 = df2 = None
+        if need1:
+            # (B, P, D) memory == channels_last (B, D, H, W)
+            df1 = gf1.reshape(B, H, W, D).permute(0, 3, 1, 2)
+        if need2:
+            # transpose of the pooling chain: level grads -> fmap2 grad
+            with torch.enable_grad():
+                x = torch.zeros(B, D, H, W, device=grad.device,
+                                dtype=torch.float32).requires_grad_(True)
+                pooled = torch_ref.alt_corr_pyramid(x, len(levels))
+                (df2,) = torch.autograd.grad(
+                    pooled, x, [a.permute(0, 3, 1, 2) for a in glv])
+        return (None, None, df1, df2, None) + (None,) * len(levels)

@@ -82,6 +82,80 @@ def corr_lookup(pyramid, coords, radius):
 
 
 # ---------------------------------------------------------------------------
+# On-demand correlation lookup (upstream RAFT's --alternate_corr mode)
+# ---------------------------------------------------------------------------
+
+def alt_corr_pyramid(fmap2, num_levels=4):
+    """Average-pool pyramid of the *second feature map*.
+
+    Pooling and the dot product are both linear, so correlating against the
+    pooled features equals pooling the correlation volume:
+    `corr_pyramid(corr_volume(f1, f2))[l][i] == <f1[:, i], levels[l]>/sqrt(D)`
+    with the same floor-mode 2x2 pooling.
+
+    In:  fmap2 (B, D, H, W).
+    Out: list of `num_levels` tensors (B, D, H/2^l, W/2^l); level 0 = input.
+    """
+    levels = [fmap2]
+    for _ in range(num_levels - 1):
+        fmap2 = F.avg_pool2d(fmap2, 2, stride=2)
+        levels.append(fmap2)
+    return levels
+
+
+def alt_corr_chunk(f1_rows, fmap2_levels, coords_rows, radius):
+    """Window lookup for one chunk of target pixels of ONE batch element.
+
+    In:  f1_rows (n, D) feature rows of the chunk's target pixels;
+         fmap2_levels — list of (D, Hl, Wl) pooled maps of that element;
+         coords_rows (n, 2) level-0 (x, y) lookup centres.
+    Out: (n, L*(2r+1)^2), channel order as `corr_lookup`.
+    Per level the (n, Hl, Wl) correlation slab is one matmul; nothing else
+    of that size exists.
+    """
+    r = radius
+    n, dim = f1_rows.shape
+    d = torch.linspace(-r, r, 2 * r + 1, device=coords_rows.device,
+                       dtype=coords_rows.dtype)
+    delta = torch.stack(torch.meshgrid(d, d, indexing="ij"), axis=-1)
+    delta = delta.view(1, 2 * r + 1, 2 * r + 1, 2)
+    out = []
+    for lvl, f2 in enumerate(fmap2_levels):
+        _, hl, wl = f2.shape
+        slab = torch.matmul(f1_rows, f2.reshape(dim, hl * wl)) / math.sqrt(dim)
+        centroid = coords_rows.reshape(n, 1, 1, 2) / 2 ** lvl
+        sampled = bilinear_sampler(slab.view(n, 1, hl, wl), centroid + delta)
+        out.append(sampled.view(n, -1))
+    return torch.cat(out, dim=-1)
+
+
+def alt_corr_lookup(fmap1, fmap2_levels, coords, radius, chunk=1024):
+    """`corr_lookup(corr_pyramid(corr_volume(f1, f2), L), coords, r)` without
+    the all-pairs volume: target pixels are processed `chunk` at a time, so
+    no more than chunk*P correlation values exist at once (under autograd the
+    slabs of all chunks are retained for the backward pass; callers that need
+    a bounded backward run the chunks one by one — see AltCorrLookupFn).
+
+    In:  fmap1 (B, D, H, W); fmap2_levels from `alt_corr_pyramid`;
+         coords (B, 2, H, W).
+    Out: (B, L*(2r+1)^2, H, W) fp32.
+    """
+    batch, dim, ht, wd = fmap1.shape
+    npix = ht * wd
+    f1 = fmap1.reshape(batch, dim, npix).transpose(1, 2)     # (B, P, D)
+    xy = coords.reshape(batch, 2, npix).transpose(1, 2)      # (B, P, 2)
+    rows = []
+    for b in range(batch):
+        lv = [f2[b] for f2 in fmap2_levels]
+        parts = [alt_corr_chunk(f1[b, s:s + chunk], lv, xy[b, s:s + chunk],
+                                radius)
+                 for s in range(0, npix, chunk)]
+        rows.append(torch.cat(parts, dim=0))
+    out = torch.stack(rows, dim=0)                           # (B, P, C)
+    return out.transpose(1, 2).reshape(batch, -1, ht, wd).contiguous().float()
+
+
+# ---------------------------------------------------------------------------
 # Normalized convolution  (reference core/nconv_modules.py:140-216)
 # ---------------------------------------------------------------------------
 
