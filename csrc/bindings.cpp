@@ -143,6 +143,15 @@ void flowhip_seq_loss_bwd_launch(const float* const* preds, float* const* dst,
                                  const float* gloss, long npix, long plane,
                                  float max_flow, float gamma, long numel_full,
                                  hipStream_t stream);
+int flowhip_nconv_bwd_fused_plan(int N, int Ci, int Co, int H, int W, int K,
+                                 int* strip);
+int flowhip_nconv_bwd_fused_ncol(int Ci, int Co, int K);
+bool flowhip_nconv_bwd_fused_launch(
+    const float* gout, const float* gcout, const float* out,
+    const float* cout, const float* data, const float* conf,
+    const float* weight, const float* bias, float* ddata, float* dconf,
+    float* partials, float* dweight, float* dbias, int N, int Ci, int Co,
+    int H, int W, int K, int strip, float eps, hipStream_t stream);
 void flowhip_nconv_bwd_prep_launch(const float* gout, const float* gcout,
                                    const float* out, const float* cout,
                                    const float* wsum, const float* bias,
@@ -1332,6 +1341,89 @@ std::vector<torch::Tensor> pacpool_bwd(torch::Tensor dy, torch::Tensor x,
 
 }  // namespace
 
+// Whole normalized-convolution backward of one layer ->
+// {ddata, dconf, dweight, dbias (empty without bias)}.
+// algo 1: the fused kernel of nconv_bwd_fused.hip (one pass + reduce);
+// algo 0: the split path (prep, bwd-data, wrw + reduce, plane sums and the
+// torch glue between them); algo -1: fused inside its envelope, else split.
+// gout or gcout may be absent (treated as zeros), not both.
+std::vector<torch::Tensor> nconv_bwd_fused(
+    c10::optional<torch::Tensor> gout, c10::optional<torch::Tensor> gcout,
+    torch::Tensor out, torch::Tensor cout, torch::Tensor data,
+    torch::Tensor conf, torch::Tensor weight,
+    c10::optional<torch::Tensor> bias, double eps, int64_t algo,
+    int64_t strip) {
+  TORCH_CHECK(algo >= -1 && algo <= 1, "nconv_bwd_fused: algo must be -1, 0, 1");
+  TORCH_CHECK(gout.has_value() || gcout.has_value(),
+              "nconv_bwd_fused: no upstream gradient");
+  for (auto* t : {&out, &cout, &data, &conf, &weight}) {
+    TORCH_CHECK(t->is_cuda() && t->is_contiguous() &&
+                t->dtype() == torch::kFloat32);
+  }
+  for (auto* t : {&gout, &gcout}) {
+    TORCH_CHECK(!t->has_value() ||
+                ((*t)->is_cuda() && (*t)->is_contiguous() &&
+                 (*t)->dtype() == torch::kFloat32 &&
+                 (*t)->sizes() == out.sizes()));
+  }
+  TORCH_CHECK(data.dim() == 4 && conf.sizes() == data.sizes() &&
+              cout.sizes() == out.sizes() && weight.dim() == 4);
+  const int N = data.size(0), Ci = data.size(1), H = data.size(2),
+            W = data.size(3);
+  const int Co = weight.size(0), K = weight.size(2);
+  TORCH_CHECK(weight.size(1) == Ci && weight.size(3) == K &&
+              out.size(0) == N && out.size(1) == Co && out.size(2) == H &&
+              out.size(3) == W);
+  if (bias.has_value())
+    TORCH_CHECK(bias->is_cuda() && bias->is_contiguous() &&
+                bias->dtype() == torch::kFloat32 && bias->numel() == Co);
+
+  int st = (int)strip;
+  const int nblocks = flowhip_nconv_bwd_fused_plan(N, Ci, Co, H, W, K, &st);
+  TORCH_CHECK(algo != 1 || nblocks > 0,
+              "nconv_bwd_fused: algo=1 forced on a shape outside the fused "
+              "envelope (K in {1,3,5}, tiled (Ci,Co) pairs, W % 4 == 0)");
+  const c10::cuda::CUDAGuard guard(data.device());
+  if (algo != 0 && nblocks > 0) {
+    auto ddata = torch::empty_like(data);
+    auto dconf = torch::empty_like(conf);
+    auto dweight = torch::empty_like(weight);
+    auto dbias = torch::empty({bias.has_value() ? (long)Co : 0L},
+                              data.options());
+    auto partials = torch::empty(
+        {nblocks, (long)flowhip_nconv_bwd_fused_ncol(Ci, Co, K)},
+        data.options());
+    hipStream_t stream = at::cuda::getCurrentCUDAStream().stream();
+    const bool ok = flowhip_nconv_bwd_fused_launch(
+        gout.has_value() ? gout->data_ptr<float>() : nullptr,
+        gcout.has_value() ? gcout->data_ptr<float>() : nullptr,
+        out.data_ptr<float>(), cout.data_ptr<float>(),
+        data.data_ptr<float>(), conf.data_ptr<float>(),
+        weight.data_ptr<float>(),
+        bias.has_value() ? bias->data_ptr<float>() : nullptr,
+        ddata.data_ptr<float>(), dconf.data_ptr<float>(),
+        partials.data_ptr<float>(), dweight.data_ptr<float>(),
+        bias.has_value() ? dbias.data_ptr<float>() : nullptr, N, Ci, Co, H, W,
+        K, st, (float)eps, stream);
+    TORCH_CHECK(ok, "nconv_bwd_fused: launch refused a planned shape");
+    return {ddata, dconf, dweight, dbias};
+  }
+
+  // split path, as NConv2dFn.backward composed it
+  auto s = weight.sum(at::IntArrayRef({1, 2, 3})).contiguous();
+  auto go = gout.has_value() ? *gout : torch::zeros_like(out);
+  auto pre = nconv_bwd_prep(go, gcout, out, cout, s, bias, eps);
+  auto r = nconv_bwd(pre[0], pre[1], data, conf, weight);
+  auto dweight = r[2];
+  if (gcout.has_value()) {
+    auto ds = -plane_sum_nchw(cout, *gcout) / s;
+    dweight = dweight + ds.view({-1, 1, 1, 1});
+  }
+  auto dbias = bias.has_value() ? plane_sum_nchw(go, c10::nullopt)
+                                : torch::empty({0}, data.options());
+  return {r[0], r[1], dweight, dbias};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "flowhip gfx950 HIP kernels";
   m.def("bgemm_nt", &bgemm_nt,
@@ -1425,4 +1517,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused elementwise preamble of nconv backward (dnomin, ddenom)");
   m.def("nconv_bwd", &nconv_bwd,
         "fused normalized convolution backward (ddata, dconf, dweight)");
+  m.def("nconv_bwd_fused", &nconv_bwd_fused,
+        "whole nconv layer backward -> (ddata, dconf, dweight, dbias); "
+        "algo 0 = split kernels, 1 = fused kernel, -1 = automatic",
+        py::arg("gout"), py::arg("gcout"), py::arg("out"), py::arg("cout"),
+        py::arg("data"), py::arg("conf"), py::arg("weight"), py::arg("bias"),
+        py::arg("eps"), py::arg("algo") = -1, py::arg("strip") = 0);
 }

@@ -114,6 +114,26 @@ class NConv2d(nn.Module):
             self.dilation, self.groups, self.eps, self.prop_conf)
         return nconv, cout
 
+    def forward_self_paired(self, inpt):
+        """forward((cat(x, x), cat(c, c))) without the cats, or None where
+        the HIP path would not run. conv(cat(x, x), w) equals
+        conv(x, w[:, :m] + w[:, m:]) and sum(w) is unchanged, so the same
+        normalized convolution runs on (x, c) at half the input channels;
+        autograd through the fold hands both halves of weight_p the same
+        gradient, which is what the duplicated channels give them."""
+        data, conf = inpt[0], inpt[1]
+        m = data.shape[1]
+        if self.groups != 1 or self.in_channels != 2 * m:
+            return None
+        weight = self.weight
+        folded = weight[:, :m] + weight[:, m:]
+        if not ops.nconv2d_uses_hip(data, folded, self.stride, self.dilation,
+                                    self.groups):
+            return None
+        return ops.nconv2d(
+            data, conf, folded, self.bias, self.stride, self.padding,
+            self.dilation, self.groups, self.eps, self.prop_conf)
+
     def extra_repr(self):
         return (f"{self.in_channels}, {self.out_channels}, "
                 f"kernel_size={self.kernel_size}, pos_fn={self.pos_fn}")
@@ -203,6 +223,14 @@ class NConvUNet(nn.Module):
         for i in range(nds):
             # fused nearest-2x upsample + concat (ops.up2x_cat; falls back
             # to interpolate+cat off-GPU or at non-2x scales)
+            if i == 0:
+                # self-paired stage: on the HIP path the (x, x) / (c, c)
+                # cats are never built (folded weight, same result up to
+                # rounding); the reference paths keep the cat bit for bit
+                folded = self.decoder[0].forward_self_paired((x[nds], c[nds]))
+                if folded is not None:
+                    x[nds + 1], c[nds + 1] = folded
+                    continue
             xin = ops.up2x_cat(x[i + nds], x[nds - i])
             cin = ops.up2x_cat(c[i + nds], c[nds - i])
             x[i + nds + 1], c[i + nds + 1] = self.decoder[i]((xin, cin))

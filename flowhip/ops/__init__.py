@@ -139,6 +139,12 @@ def nconv2d(data, conf, weight, bias=None, stride=1, padding=0, dilation=1,
                              dilation, groups, eps, prop_conf)
 
 
+def nconv2d_uses_hip(data, weight, stride=1, dilation=1, groups=1):
+    """True where nconv2d would run the HIP kernels for these arguments."""
+    return _ext.use_hip(data) and _can_fuse_nconv(weight, stride, dilation,
+                                                  groups)
+
+
 def _can_fuse_nconv(weight, stride, dilation, groups):
     from torch.nn.modules.utils import _pair
     if _pair(stride) != (1, 1) or _pair(dilation) != (1, 1) or groups != 1:
