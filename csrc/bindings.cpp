@@ -25,6 +25,12 @@ bool flowhip_alt_corr_lookup_fwd_launch(const void* f1,
                                         int BP, int P, int D, int L,
                                         int radius, int cl, int ldc,
                                         int out_bf16, hipStream_t stream);
+bool flowhip_alt_corr_lookup_bwd_launch(
+    const void* f1, const void* const* levels, float* const* accs,
+    const int* Hs, const int* Ws, const float* coords, const void* grad,
+    float* df1, float* df2, int B, int H, int W, int D, int L, int radius,
+    int cl, int ldc, int g_bf16, int need_f1, int need_f2, int algo,
+    hipStream_t stream);
 void flowhip_corr_lookup_bwd_launch(const void* gout, const float* coords,
                                     void* const* glevels, const int* Hs,
                                     const int* Ws, int BP, int P,
@@ -286,6 +292,10 @@ torch::Tensor corr_lookup_fwd(std::vector<torch::Tensor> pyramid,
   return out;
 }
 
+// what algo == "auto" selects in alt_corr_lookup_bwd: 0 = direct, 1 = tiled
+// (measured table in profiles/README.md, "On-demand correlation lookup")
+#define ALT_CORR_BWD_AUTO_ALGO 1
+
 bool alt_corr_supported(int64_t D, int64_t radius, int64_t L) {
   return flowhip_alt_corr_supported((int)D, (int)radius, (int)L);
 }
@@ -356,6 +366,119 @@ torch::Tensor alt_corr_lookup_fwd(torch::Tensor f1,
       out_bf16 ? 1 : 0, stream);
   TORCH_CHECK(ok, "alt_corr_lookup: unsupported configuration");
   return out;
+}
+
+// Backward of alt_corr_lookup_fwd (alt_corr_bwd.hip). `grad` has the layout
+// of the forward's output: contiguous NCHW, or the NHWC view of rows with
+// the 8-aligned stride (pad tail never read); fp32 or bf16. Returns
+// (df1_rows (B,P,D) fp32 | None, df2 (B,D,H,W) fp32 channels-last | None).
+// algo: "direct" (atomics per patch position), "tiled" (LDS box per 4x4
+// pixel tile) or "auto" (the measured pick, profiles/README.md).
+std::tuple<c10::optional<torch::Tensor>, c10::optional<torch::Tensor>>
+alt_corr_lookup_bwd(torch::Tensor grad, torch::Tensor f1,
+                    std::vector<torch::Tensor> levels, torch::Tensor coords,
+                    int64_t radius, bool channels_last, bool need_f1,
+                    bool need_f2, const std::string& algo) {
+  TORCH_CHECK(!levels.empty() && levels.size() <= 4,
+              "alt_corr_lookup_bwd: 1..4 levels");
+  TORCH_CHECK(coords.is_cuda() && coords.dtype() == torch::kFloat32 &&
+              coords.is_contiguous() && coords.dim() == 4 &&
+              coords.size(1) == 2,
+              "alt_corr_lookup_bwd: coords must be contiguous fp32 (B,2,H,W)");
+  const int B = coords.size(0), H = coords.size(2), W = coords.size(3);
+  const int P = H * W;
+  const int L = (int)levels.size();
+  const int K = 2 * (int)radius + 1;
+  TORCH_CHECK(f1.is_cuda() && f1.dtype() == torch::kBFloat16 &&
+              f1.is_contiguous() && f1.dim() == 3,
+              "alt_corr_lookup_bwd: f1 must be contiguous bf16 (B,P,D)");
+  TORCH_CHECK(f1.size(0) == B && f1.size(1) == P,
+              "alt_corr_lookup_bwd: f1 / coords shape mismatch");
+  const int D = f1.size(2);
+  TORCH_CHECK(flowhip_alt_corr_supported(D, (int)radius, L),
+              "alt_corr_lookup_bwd: unsupported D / radius / levels");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(f1.data_ptr()) & 15) == 0,
+              "alt_corr_lookup_bwd: f1 must be 16-byte aligned");
+
+  const void* ptrs[4] = {nullptr, nullptr, nullptr, nullptr};
+  int Hs[4] = {0, 0, 0, 0}, Ws[4] = {0, 0, 0, 0};
+  int64_t cells = 0;
+  for (int l = 0; l < L; ++l) {
+    auto& lvl = levels[l];
+    TORCH_CHECK(lvl.is_cuda() && lvl.is_contiguous() &&
+                lvl.dtype() == torch::kBFloat16 && lvl.dim() == 4,
+                "alt_corr_lookup_bwd: contiguous bf16 (B,Hl,Wl,D) levels "
+                "required");
+    TORCH_CHECK(lvl.size(0) == B && lvl.size(3) == D,
+                "alt_corr_lookup_bwd: level batch / channel mismatch");
+    TORCH_CHECK(lvl.size(1) >= 1 && lvl.size(2) >= 1,
+                "alt_corr_lookup_bwd: empty level");
+    TORCH_CHECK((reinterpret_cast<uintptr_t>(lvl.data_ptr()) & 15) == 0,
+                "alt_corr_lookup_bwd: levels must be 16-byte aligned");
+    ptrs[l] = lvl.data_ptr();
+    Hs[l] = lvl.size(1);
+    Ws[l] = lvl.size(2);
+    cells += (int64_t)B * Hs[l] * Ws[l];
+  }
+  TORCH_CHECK(Hs[0] == H && Ws[0] == W,
+              "alt_corr_lookup_bwd: level 0 must match the coords grid");
+
+  const int64_t C = (int64_t)L * K * K;
+  const int64_t C8 = channels_last ? (C + 7) / 8 * 8 : C;
+  const bool g_bf16 = grad.dtype() == torch::kBFloat16;
+  TORCH_CHECK(grad.is_cuda() && (g_bf16 || grad.dtype() == torch::kFloat32),
+              "alt_corr_lookup_bwd: grad must be fp32 or bf16 on the GPU");
+  TORCH_CHECK(grad.dim() == 4 && grad.size(0) == B && grad.size(1) == C &&
+              grad.size(2) == H && grad.size(3) == W,
+              "alt_corr_lookup_bwd: grad must be (B, L*K*K, H, W)");
+  if (channels_last) {
+    TORCH_CHECK(grad.stride(1) == 1 && grad.stride(3) == C8 &&
+                grad.stride(2) == (int64_t)W * C8 &&
+                (B == 1 || grad.stride(0) == (int64_t)P * C8),
+                "alt_corr_lookup_bwd: grad must have the forward output's "
+                "NHWC strides (8-aligned channel stride)");
+  } else {
+    TORCH_CHECK(grad.is_contiguous(),
+                "alt_corr_lookup_bwd: grad must be contiguous NCHW");
+  }
+  int algo_id;
+  if (algo == "direct") {
+    algo_id = 0;
+  } else if (algo == "tiled") {
+    algo_id = 1;
+  } else {
+    TORCH_CHECK(algo == "auto", "alt_corr_lookup_bwd: algo must be auto, "
+                "direct or tiled");
+    algo_id = ALT_CORR_BWD_AUTO_ALGO;
+  }
+
+  const c10::cuda::CUDAGuard guard(coords.device());
+  const auto fopt = coords.options().dtype(torch::kFloat32);
+  c10::optional<torch::Tensor> df1, df2;
+  torch::Tensor d1, d2, acc;
+  float* accs[4] = {nullptr, nullptr, nullptr, nullptr};
+  if (need_f1) d1 = torch::empty({B, P, D}, fopt);
+  if (need_f2) {
+    d2 = torch::empty({B, H, W, D}, fopt);
+    // one zero-initialised allocation holds every level's accumulator
+    acc = torch::zeros({cells * D}, fopt);
+    int64_t off = 0;
+    for (int l = 0; l < L; ++l) {
+      accs[l] = acc.data_ptr<float>() + off;
+      off += (int64_t)B * Hs[l] * Ws[l] * D;
+    }
+  }
+  hipStream_t stream = at::cuda::getCurrentCUDAStream().stream();
+  bool ok = flowhip_alt_corr_lookup_bwd_launch(
+      f1.data_ptr(), ptrs, accs, Hs, Ws, coords.data_ptr<float>(),
+      grad.data_ptr(), need_f1 ? d1.data_ptr<float>() : nullptr,
+      need_f2 ? d2.data_ptr<float>() : nullptr, B, H, W, D, L, (int)radius,
+      channels_last ? 1 : 0, (int)C8, g_bf16 ? 1 : 0, need_f1 ? 1 : 0,
+      need_f2 ? 1 : 0, algo_id, stream);
+  TORCH_CHECK(ok, "alt_corr_lookup_bwd: unsupported configuration");
+  if (need_f1) df1 = d1;
+  if (need_f2) df2 = d2.permute({0, 3, 1, 2});
+  return {df1, df2};
 }
 
 std::vector<torch::Tensor> corr_lookup_bwd(torch::Tensor gout,
@@ -1436,6 +1559,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "on-demand correlation window lookup from feature maps");
   m.def("alt_corr_supported", &alt_corr_supported,
         "alt_corr_lookup_fwd envelope (D, radius, levels)");
+  m.def("alt_corr_lookup_bwd", &alt_corr_lookup_bwd,
+        "backward of alt_corr_lookup_fwd: (df1_rows | None, df2 | None)",
+        py::arg("grad"), py::arg("f1_rows"), py::arg("levels"),
+        py::arg("coords"), py::arg("radius"), py::arg("channels_last"),
+        py::arg("need_f1") = true, py::arg("need_f2") = true,
+        py::arg("algo") = "auto");
   m.def("corr_lookup_bwd", &corr_lookup_bwd,
         "backward of corr_lookup_fwd (pyramid grads; accumulates into "
         "`prev` when the pyramid is iteration-chained)",

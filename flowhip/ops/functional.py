@@ -14,6 +14,7 @@ not inherited from the reference):
 """
 
 import math
+import os
 
 import torch
 
@@ -215,6 +216,28 @@ def alt_f2_levels(fmap2, num_levels):
             x.permute(0, 2, 3, 1).to(torch.bfloat16).contiguous() for x in lv)
 
 
+def _alt_grad_layout(grad, cl):
+    """The cotangent in the layout `alt_corr_lookup_fwd` emits (what
+    `alt_corr_lookup_bwd` reads): contiguous NCHW, or NHWC rows with the
+    8-aligned channel stride. A cotangent that already has it passes through;
+    any other is copied (the pad tail is never read, so it stays
+    uninitialised)."""
+    if grad.dtype not in (torch.float32, torch.bfloat16):
+        grad = grad.float()
+    if not cl:
+        return grad.contiguous()
+    B, C, H, W = grad.shape
+    c8 = (C + 7) // 8 * 8
+    want = (H * W * c8, 1, W * c8, c8)
+    if all(grad.shape[d] == 1 or grad.stride(d) == want[d] for d in range(4)):
+        return grad.as_strided(grad.shape, want)
+    full = torch.empty((B, c8, H, W), device=grad.device, dtype=grad.dtype,
+                       memory_format=torch.channels_last)
+    g = full.narrow(1, 0, C)
+    g.copy_(grad)
+    return g
+
+
 class AltCorrLookupFn(torch.autograd.Function):
     """On-demand correlation window lookup (`--alternate_corr`): what
     CorrLookupFn gathers out of the all-pairs pyramid, computed from the
@@ -227,13 +250,20 @@ class AltCorrLookupFn(torch.autograd.Function):
     be detached, as for CorrLookupFn. Only coords, f1_rows and the levels
     are saved.
 
-    backward returns gradients for fmap1 and fmap2. There is no HIP backward
-    kernel: the window correlations are recomputed with torch ops in chunks
-    of target pixels (one (chunk, Hl, Wl) slab per level, at most
-    `_ALT_BWD_SLAB` elements at level 0) and differentiated chunk by chunk,
-    so the backward never allocates more than that fixed slab plus O(P*D)
-    accumulators. Each lookup of the iteration loop repeats the recompute:
-    training in this mode is memory-bounded, not tuned (cost on file in
+    backward returns gradients for fmap1 and fmap2 from `alt_corr_lookup_bwd`
+    (csrc/alt_corr_bwd.hip): the transposed window blend per (pixel, level),
+    df1 rows summed in registers, level gradients of f2 summed with float
+    atomics into fp32 accumulators (so df2 is not bit-reproducible) and
+    gathered back through the pooling chain by one kernel. It allocates
+    df1, df2 and the level accumulators, about 3.33 * P * D * 4 bytes, and
+    nothing that grows with P^2. `needs_input_grad` selects what is
+    computed; a cotangent in another layout than the forward's output is
+    copied into it first.
+
+    FLOWHIP_ALT_CORR_BWD=torch|direct|tiled forces a path: `torch` is the
+    chunked recompute with torch matmuls (`_backward_torch`, up to
+    `_ALT_BWD_SLAB` floats per slab), `direct` and `tiled` the two HIP
+    scatter forms; unset, the binding's measured pick runs (table in
     profiles/README.md).
     """
 
@@ -249,17 +279,44 @@ class AltCorrLookupFn(torch.autograd.Function):
             corr_bf16_enabled())
         ctx.save_for_backward(coords_c, f1_rows, *levels)
         ctx.radius = int(radius)
+        ctx.cl = cl
         ctx.fmap_shape = None if fmap1 is None else tuple(fmap1.shape)
         return out
 
     @staticmethod
     def backward(ctx, grad):
-        from . import torch_ref
         coords, f1_rows, *levels = ctx.saved_tensors
-        B, P, D = f1_rows.shape
         need1, need2 = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
         if not (need1 or need2):
             return (None,) * (5 + len(levels))
+        mode = os.environ.get("FLOWHIP_ALT_CORR_BWD", "") or "auto"
+        if mode not in ("auto", "torch", "direct", "tiled"):
+            raise ValueError(
+                f"FLOWHIP_ALT_CORR_BWD={mode!r}: expected torch, direct or "
+                "tiled")
+        if mode == "torch":
+            df1, df2 = AltCorrLookupFn._backward_torch(
+                ctx, grad, coords, f1_rows, levels, need1, need2)
+        else:
+            B, P, D = f1_rows.shape
+            H, W = coords.shape[-2:]
+            g = _alt_grad_layout(grad, ctx.cl)
+            rows, df2 = _ext.ext().alt_corr_lookup_bwd(
+                g, f1_rows, list(levels), coords, ctx.radius, ctx.cl,
+                bool(need1), bool(need2), mode)
+            # (B, P, D) memory == channels_last (B, D, H, W)
+            df1 = (rows.reshape(B, H, W, D).permute(0, 3, 1, 2)
+                   if need1 else None)
+        return (None, None, df1, df2, None) + (None,) * len(levels)
+
+    @staticmethod
+    def _backward_torch(ctx, grad, coords, f1_rows, levels, need1, need2):
+        """FLOWHIP_ALT_CORR_BWD=torch: the chunked recompute with torch
+        matmuls (one (chunk, Hl, Wl) slab per level, at most
+        `_ALT_BWD_SLAB` elements at level 0); baseline of the HIP backward
+        in tests and tools/bench_alt_corr_bwd.py."""
+        from . import torch_ref
+        B, P, D = f1_rows.shape
         H, W = coords.shape[-2:]
         g = grad.float().reshape(B, -1, P).transpose(1, 2)      # (B, P, C)
         xy = coords.reshape(B, 2, P).transpose(1, 2)            # (B, P, 2)
@@ -297,4 +354,4 @@ class AltCorrLookupFn(torch.autograd.Function):
                 pooled = torch_ref.alt_corr_pyramid(x, len(levels))
                 (df2,) = torch.autograd.grad(
                     pooled, x, [a.permute(0, 3, 1, 2) for a in glv])
-        return (None, None, df1, df2, None) + (None,) * len(levels)
+        return df1, df2
