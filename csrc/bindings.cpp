@@ -105,6 +105,19 @@ bool flowhip_conv_gemm_wrw_launch(const void* dy, const void* x,
                                   int Cin, int Cout, int cpad, int KH,
                                   int KW, int padH, int padW, int nchunk,
                                   int algo, hipStream_t stream);
+bool flowhip_conv_gemm_wrw_partials_launch(
+    const void* dy, const void* x, const void* x2, float* partials,
+    float* biasp, const void* zpage, long Mtot, int HH, int WW, int srcH,
+    int srcW, int sH, int sW, int ld_x, int ld_x2, int C1, int Cin, int Cout,
+    int cpad, int KH, int KW, int padH, int padW, int nchunk, int algo,
+    bool accumulate, hipStream_t stream);
+void flowhip_conv_gemm_wrw_finish_launch(const float* partials,
+                                         const float* biasp, float* dw,
+                                         float* dbias, int Cin, int Cout,
+                                         int cpad, int KH, int KW, int nchunk,
+                                         bool accumulate,
+                                         hipStream_t stream);
+bool flowhip_conv_gemm_wrw_accumulate_wins(int path);
 int flowhip_conv_gemm_wrw_plan(long Mtot, int HH, int WW, int srcH, int srcW,
                                int sH, int sW, bool has_x2, int C1, int Cout,
                                int cpad, int KH, int KW, int padH, int padW,
@@ -1217,6 +1230,162 @@ std::vector<torch::Tensor> conv_gemm_wrw(torch::Tensor dy, torch::Tensor x,
   return {dw, dbias};
 }
 
+// The same weight gradient as three steps, for callers that sum the
+// gradients of several calls (same weights, same shapes) in one partials
+// buffer and reduce once: plan -> partials (accumulate) x K -> finish.
+namespace {
+struct WrwGeom {
+  int N, C1, H, W, OH, OW, Cin, Cout, cpad, tiles_o, ld_x, ld_x2;
+  long Mtot;
+  const void* x2p;
+};
+
+WrwGeom wrw_geom(const torch::Tensor& dy, const torch::Tensor& x,
+                 const c10::optional<torch::Tensor>& x2) {
+  WrwGeom g;
+  g.ld_x2 = 0;
+  cg_check_x(x, g.ld_x);
+  TORCH_CHECK(dy.is_cuda() && dy.dim() == 4 &&
+              dy.scalar_type() == torch::kBFloat16 && dy.stride(1) == 1 &&
+              dy.stride(3) == dy.size(1),
+              "conv_gemm_wrw: dy must be channels-last contiguous");
+  g.N = x.size(0); g.C1 = x.size(1); g.H = x.size(2); g.W = x.size(3);
+  g.OH = dy.size(2); g.OW = dy.size(3);
+  TORCH_CHECK(dy.size(0) == g.N);
+  g.Cin = g.C1;
+  g.x2p = nullptr;
+  if (x2.has_value()) {
+    cg_check_x(x2.value(), g.ld_x2);
+    TORCH_CHECK(x2->size(0) == g.N && x2->size(2) == g.H &&
+                x2->size(3) == g.W);
+    g.Cin = g.C1 + (int)x2->size(1);
+    g.x2p = x2->data_ptr();
+  }
+  g.Cout = dy.size(1);
+  g.Mtot = (long)g.N * g.OH * g.OW;
+  g.cpad = (g.Cin + 63) / 64 * 64;
+  g.tiles_o = (g.Cout + 63) / 64;
+  return g;
+}
+
+long wrw_buffer_numel(const WrwGeom& g, int64_t KH, int64_t KW, int nchunk,
+                      bool want_bias) {
+  return (long)nchunk * KH * KW * g.tiles_o * 64 * g.cpad +
+         (want_bias ? (long)nchunk * g.tiles_o * 64 : 0);
+}
+}  // namespace
+
+// -> (path, nchunk, buffer elements, accumulate). The buffer size includes
+// the bias partials when want_bias. accumulate: 1 where calls that share a
+// weight should sum their partials in one buffer, 0 where they should run
+// one-shot partials and add each finish to a running dW.
+std::vector<int64_t> conv_gemm_wrw_plan(torch::Tensor dy, torch::Tensor x,
+                                        c10::optional<torch::Tensor> x2,
+                                        int64_t KH, int64_t KW, int64_t sH,
+                                        int64_t sW, bool want_bias,
+                                        int64_t algo, int64_t nchunk_req) {
+  const WrwGeom g = wrw_geom(dy, x, x2);
+  TORCH_CHECK(algo >= -1 && algo <= 1, "conv_gemm_wrw: algo must be -1, 0, 1");
+  int nchunk = 1;
+  const int path = flowhip_conv_gemm_wrw_plan(
+      g.Mtot, g.OH, g.OW, g.H, g.W, (int)sH, (int)sW, g.x2p != nullptr, g.C1,
+      g.Cout, g.cpad, (int)KH, (int)KW, (int)KH / 2, (int)KW / 2, (int)algo,
+      (int)nchunk_req, &nchunk);
+  TORCH_CHECK(path >= 0,
+              "conv_gemm_wrw: algo=1 (halo) forced on a shape outside its "
+              "envelope (stride 1, same padding, 3x3 / 1x5 / 5x1)");
+  return {path, nchunk, wrw_buffer_numel(g, KH, KW, nchunk, want_bias),
+          flowhip_conv_gemm_wrw_accumulate_wins(path) ? 1 : 0};
+}
+
+// One partials launch into the caller's buffer; no reduce. algo / nchunk:
+// what conv_gemm_wrw_plan returned for these shapes (checked again here,
+// because a wrong pair would size the grid past the buffer).
+void conv_gemm_wrw_partials(torch::Tensor dy, torch::Tensor x,
+                            c10::optional<torch::Tensor> x2,
+                            torch::Tensor partials, int64_t KH, int64_t KW,
+                            int64_t sH, int64_t sW, bool want_bias,
+                            bool accumulate, int64_t algo, int64_t nchunk) {
+  const WrwGeom g = wrw_geom(dy, x, x2);
+  TORCH_CHECK(algo == 0 || algo == 1,
+              "conv_gemm_wrw_partials: algo must be a planned path (0 | 1)");
+  int planned = 0;
+  const int path = flowhip_conv_gemm_wrw_plan(
+      g.Mtot, g.OH, g.OW, g.H, g.W, (int)sH, (int)sW, g.x2p != nullptr, g.C1,
+      g.Cout, g.cpad, (int)KH, (int)KW, (int)KH / 2, (int)KW / 2, (int)algo,
+      (int)nchunk, &planned);
+  TORCH_CHECK(path == algo && planned == nchunk && nchunk >= 1,
+              "conv_gemm_wrw_partials: (algo, nchunk) is not a plan for "
+              "these shapes");
+  TORCH_CHECK(partials.is_cuda() && partials.is_contiguous() &&
+              partials.scalar_type() == torch::kFloat32 &&
+              partials.device() == x.device() &&
+              partials.numel() ==
+                  wrw_buffer_numel(g, KH, KW, (int)nchunk, want_bias),
+              "conv_gemm_wrw_partials: buffer does not match the plan");
+  float* pp = partials.data_ptr<float>();
+  float* biasp =
+      want_bias ? pp + wrw_buffer_numel(g, KH, KW, (int)nchunk, false)
+                : nullptr;
+  const c10::cuda::CUDAGuard guard(x.device());
+  hipStream_t stream = at::cuda::getCurrentCUDAStream().stream();
+  const bool launched = flowhip_conv_gemm_wrw_partials_launch(
+      dy.data_ptr(), x.data_ptr(), g.x2p, pp, biasp, cg_zero_page(), g.Mtot,
+      g.OH, g.OW, g.H, g.W, (int)sH, (int)sW, g.ld_x, g.ld_x2, g.C1, g.Cin,
+      g.Cout, g.cpad, (int)KH, (int)KW, (int)KH / 2, (int)KW / 2, (int)nchunk,
+      (int)algo, accumulate, stream);
+  TORCH_CHECK(launched,
+              "conv_gemm_wrw: the halo kernel refused a planned shape");
+}
+
+// Reduce a partials buffer to [dw (Cout, Cin, KH, KW), dbias (Cout)]. With
+// dw_into (and dbias_into when want_bias) the sums are added to those
+// tensors in place and they are returned.
+std::vector<torch::Tensor> conv_gemm_wrw_finish(
+    torch::Tensor partials, int64_t Cout, int64_t Cin, int64_t KH,
+    int64_t KW, bool want_bias, int64_t nchunk,
+    c10::optional<torch::Tensor> dw_into,
+    c10::optional<torch::Tensor> dbias_into) {
+  TORCH_CHECK(Cout >= 1 && Cin >= 1 && KH >= 1 && KW >= 1 && nchunk >= 1);
+  const long cpad = (Cin + 63) / 64 * 64;
+  const long orows = (Cout + 63) / 64 * 64;
+  const long wnumel = nchunk * KH * KW * orows * cpad;
+  TORCH_CHECK(partials.is_cuda() && partials.is_contiguous() &&
+              partials.scalar_type() == torch::kFloat32 &&
+              partials.numel() == wnumel + (want_bias ? nchunk * orows : 0),
+              "conv_gemm_wrw_finish: buffer does not match the shapes");
+  const bool accumulate = dw_into.has_value();
+  TORCH_CHECK(dbias_into.has_value() == (accumulate && want_bias),
+              "conv_gemm_wrw_finish: dw_into and dbias_into go together");
+  torch::Tensor dw, dbias;
+  if (accumulate) {
+    dw = dw_into.value();
+    TORCH_CHECK(dw.is_contiguous() && dw.device() == partials.device() &&
+                dw.scalar_type() == torch::kFloat32 &&
+                dw.sizes() == at::IntArrayRef({Cout, Cin, KH, KW}),
+                "conv_gemm_wrw_finish: dw_into does not match the shapes");
+    if (want_bias) {
+      dbias = dbias_into.value();
+      TORCH_CHECK(dbias.is_contiguous() &&
+                  dbias.device() == partials.device() &&
+                  dbias.scalar_type() == torch::kFloat32 &&
+                  dbias.dim() == 1 && dbias.size(0) == Cout,
+                  "conv_gemm_wrw_finish: dbias_into does not match");
+    }
+  } else {
+    dw = torch::empty({Cout, Cin, KH, KW}, partials.options());
+    if (want_bias) dbias = torch::empty({Cout}, partials.options());
+  }
+  const float* pp = partials.data_ptr<float>();
+  const c10::cuda::CUDAGuard guard(partials.device());
+  hipStream_t stream = at::cuda::getCurrentCUDAStream().stream();
+  flowhip_conv_gemm_wrw_finish_launch(
+      pp, want_bias ? pp + wnumel : nullptr, dw.data_ptr<float>(),
+      want_bias ? dbias.data_ptr<float>() : nullptr, (int)Cin, (int)Cout,
+      (int)cpad, (int)KH, (int)KW, (int)nchunk, accumulate, stream);
+  return {dw, dbias};
+}
+
 torch::Tensor col_sum_bf16(torch::Tensor dy) {
   TORCH_CHECK(dy.is_cuda() && dy.dim() == 4 &&
               dy.scalar_type() == torch::kBFloat16 && dy.stride(1) == 1 &&
@@ -1628,6 +1797,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("KW"), py::arg("sH") = 1, py::arg("sW") = 1,
         py::arg("want_bias") = false, py::arg("algo") = -1,
         py::arg("nchunk") = 0);
+  m.def("conv_gemm_wrw_plan", &conv_gemm_wrw_plan,
+        "weight-gradient plan for these shapes: [path, nchunk, partials "
+        "buffer elements, accumulate (1: sum shared calls in the buffer)]",
+        py::arg("dy"), py::arg("x"), py::arg("x2"), py::arg("KH"),
+        py::arg("KW"), py::arg("sH") = 1, py::arg("sW") = 1,
+        py::arg("want_bias") = false, py::arg("algo") = -1,
+        py::arg("nchunk") = 0);
+  m.def("conv_gemm_wrw_partials", &conv_gemm_wrw_partials,
+        "one split-M partials launch into a caller-supplied buffer, no "
+        "reduce; accumulate adds to the buffer instead of overwriting it",
+        py::arg("dy"), py::arg("x"), py::arg("x2"), py::arg("partials"),
+        py::arg("KH"), py::arg("KW"), py::arg("sH"), py::arg("sW"),
+        py::arg("want_bias"), py::arg("accumulate"), py::arg("algo"),
+        py::arg("nchunk"));
+  m.def("conv_gemm_wrw_finish", &conv_gemm_wrw_finish,
+        "reduce a partials buffer over its chunks; returns [dw, dbias], "
+        "added in place to dw_into / dbias_into when given",
+        py::arg("partials"), py::arg("Cout"), py::arg("Cin"), py::arg("KH"),
+        py::arg("KW"), py::arg("want_bias"), py::arg("nchunk"),
+        py::arg("dw_into") = py::none(), py::arg("dbias_into") = py::none());
   m.def("instnorm_cl_fwd", &instnorm_cl_fwd,
         "channels-last InstanceNorm2d forward (y, mean, rstd)");
   m.def("instnorm_cl_bwd", &instnorm_cl_bwd,

@@ -339,7 +339,7 @@ __global__ __launch_bounds__(CG_THREADS, 2) void conv_gemm_wrw_kernel(
     const __bf16* __restrict__ zpage,
     long Mtot, int HH, int WW, int srcH, int srcW, int sH, int sW, int ld_x,
     int ld_x2, int C1, int Cin, int Cout, int cpad, int KH, int KW, int padH,
-    int padW, int tiles_o, int tiles_c, int nchunk) {
+    int padW, int tiles_o, int tiles_c, int nchunk, int accumulate) {
   __shared__ __attribute__((aligned(16))) char lds[2 * 2 * CG_BM * CG_BK * 2];
 
   const int tid = threadIdx.x;
@@ -531,13 +531,36 @@ __global__ __launch_bounds__(CG_THREADS, 2) void conv_gemm_wrw_kernel(
     cur ^= 1;
   }
 
-  // store partial tile: partials[chunk][kyx][o0+...][c0+...]
+  // store partial tile: partials[chunk][kyx][o0+...][c0+...]. accumulate:
+  // add to the slot instead (the sum over the calls that share the buffer).
+  // A slot has exactly one owning workgroup and thread, so this is a plain
+  // load/add/store, no atomics, and the sum order is the call order.
   const int KYX = KH * KW;
   const int orows = tiles_o * 64;
   float* pbase = partials +
                  (((long)chunk * KYX + kyx) * orows) * cpad;
   const int fcol = lane & 15;
   const int frow0 = (lane >> 4) * 4;
+  if (accumulate) {
+    // all 16 loads first: issued one by one between the stores, each
+    // would wait for a full memory round trip (the compiler cannot prove
+    // that a load does not alias the store before it)
+    float prev[2][2][4];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          prev[i][j][r] = pbase[(long)(o0 + wr + i * 16 + frow0 + r) * cpad +
+                                c0 + wc + j * 16 + fcol];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[i][j][r] += prev[i][j][r];
+  }
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
 #pragma unroll
@@ -559,36 +582,51 @@ __global__ __launch_bounds__(CG_THREADS, 2) void conv_gemm_wrw_kernel(
       float s = bacc[i];
       s += __shfl_xor(s, 16, 64);
       s += __shfl_xor(s, 32, 64);
-      if (lane < 16)
-        biasp[(long)chunk * (tiles_o * 64) + o0 + wr + i * 16 + lane] = s;
+      if (lane < 16) {
+        float* bp = biasp + (long)chunk * (tiles_o * 64) + o0 + wr + i * 16 +
+                    lane;
+        if (accumulate) s += *bp;
+        *bp = s;
+      }
     }
   }
 }
 
-// reduce partials over chunks and scatter into dW (Cout, Cin, KH, KW) fp32
+// reduce partials over chunks (ascending) and scatter into dW (Cout, Cin,
+// KH, KW) fp32. Consecutive threads take consecutive c of one (kyx, o)
+// row, so every chunk's read is one contiguous run; the writes are KYX
+// floats apart, but there are nchunk times fewer of them. (With kyx
+// fastest, each thread of a wave read a different orows*cpad plane: 2x
+// slower on the 27 MB halo buffers. One thread per (o, c) looping over kyx
+// reads as well but leaves too few threads: up to 5x slower. Figures:
+// profiles/README.md round 5.)
+// accumulate: dW += the sum (and dbias), the fp32 add autograd would do
+// between two calls that share a weight, without its launch.
 __global__ __launch_bounds__(CG_THREADS) void conv_gemm_wrw_reduce_kernel(
     const float* __restrict__ partials, float* __restrict__ dw,
     const float* __restrict__ biasp, float* __restrict__ dbias,
-    int nchunk, int KYX, int orows, int cpad, int Cout, int Cin) {
+    int nchunk, int KYX, int orows, int cpad, int Cout, int Cin,
+    int accumulate) {
   if (dbias)
     for (int o = blockIdx.x * CG_THREADS + threadIdx.x; o < Cout;
          o += gridDim.x * CG_THREADS) {
       float s = 0.f;
       for (int ch = 0; ch < nchunk; ++ch) s += biasp[(long)ch * orows + o];
-      dbias[o] = s;
+      dbias[o] = accumulate ? dbias[o] + s : s;
     }
   const long total = (long)Cout * Cin * KYX;
   for (long idx = (long)blockIdx.x * CG_THREADS + threadIdx.x; idx < total;
        idx += (long)gridDim.x * CG_THREADS) {
     long t = idx;
-    const int kyx = (int)(t % KYX); t /= KYX;
     const int c = (int)(t % Cin); t /= Cin;
-    const int o = (int)t;
+    const int o = (int)(t % Cout); t /= Cout;
+    const int kyx = (int)t;
     float s = 0.f;
     for (int ch = 0; ch < nchunk; ++ch)
       s += partials[((((long)ch * KYX + kyx) * orows) + o) * cpad + c];
     // dw layout (O, I, KH, KW): kyx = ky*KW + kx
-    dw[((long)o * Cin + c) * KYX + kyx] = s;
+    float* d = dw + ((long)o * Cin + c) * KYX + kyx;
+    *d = accumulate ? *d + s : s;
   }
 }
 
@@ -674,7 +712,8 @@ bool flowhip_conv_wrw_halo_launch(const void* dy, const void* x,
                                   float* biasp, const void* zpage, int N,
                                   int H, int W, int ld_x, int ld_x2, int C1,
                                   int Cin, int Cout, int cpad, int KH, int KW,
-                                  int nchunk, hipStream_t stream);
+                                  int nchunk, bool accumulate,
+                                  hipStream_t stream);
 
 // Chooses the weight-gradient path and its split-M chunk count; the caller
 // sizes the partials buffer (nchunk * KYX * tiles_o*64 * cpad weight
@@ -737,8 +776,94 @@ int flowhip_conv_gemm_wrw_plan(long Mtot, int HH, int WW, int srcH, int srcW,
   return 0;
 }
 
-// algo / nchunk: as returned by flowhip_conv_gemm_wrw_plan. Returns false
-// (nothing launched) if the halo kernel refuses a planned shape.
+// Whether calls that share a weight should sum their partials in one
+// buffer (partials launch with accumulate, one finish at the end) or run
+// one-shot partials and add each call's reduce to a running dW (finish
+// with accumulate). Measured per backward pass of 12 calls at 3x56x128 on
+// MI355X (tools/bench_wrw.py --accumulate, median of 5 alternating rounds,
+// min-max within 1%; profiles/README.md round 5). Columns: 12 one-shot
+// calls + 11 fp32 adds of dW and dbias | 12 accumulating calls + 1 finish
+// | 12 one-shot partials each with a finish into the running dW; in us.
+//   generic path: accumulating partials wins on every shape
+//     128->64 3x3    428 | 215 | 385      256->2 3x3    453 | 321 | 414
+//     324->256 1x1   491 | 320 | 456      8->128 7x7    702 | 614 | 666
+//   halo path: accumulating partials loses on every shape, the finish
+//   into the running dW wins
+//     256->192 3x3   705 |  965 | 665     384->256 1x5  818 |  939 | 774
+//     256->126 3x3   593 |  817 | 554     384->256 5x1  911 | 1037 | 867
+//     128->256 3x3   595 |  741 | 554     384->128 1x5  567 |  643 | 528
+//                                         384->128 5x1  613 |  700 | 575
+// The halo kernel owns its CU at one wave per SIMD, so nothing hides the
+// latency of its epilogue's 16 * KYX loads per thread, and in the training
+// step its 15-27 MB buffers leave the cache between two iterations: +41 us
+// per launch in the kernel trace, against 13 us of reduce and 9 us of adds
+// saved. The rule follows the two measured classes.
+bool flowhip_conv_gemm_wrw_accumulate_wins(int path) { return path == 0; }
+
+// The weight gradient runs in two steps that share one partials buffer.
+// algo / nchunk: as returned by flowhip_conv_gemm_wrw_plan.
+//
+// Step 1, partials: one launch of the planned partials kernel. accumulate
+// == false overwrites every slot of the buffer the reduce will read (no
+// zero-fill needed); accumulate == true adds this call's sums to what the
+// buffer holds, so K calls with the same weights (the refinement loop)
+// leave the sum of their K gradients in the slots and need ONE reduce.
+// biasp == nullptr skips the bias gradient. Returns false (nothing
+// launched) if the halo kernel refuses a planned shape.
+bool flowhip_conv_gemm_wrw_partials_launch(
+    const void* dy, const void* x, const void* x2, float* partials,
+    float* biasp, const void* zpage, long Mtot, int HH, int WW, int srcH,
+    int srcW, int sH, int sW, int ld_x, int ld_x2, int C1, int Cin, int Cout,
+    int cpad, int KH, int KW, int padH, int padW, int nchunk, int algo,
+    bool accumulate, hipStream_t stream) {
+  const int tiles_o = fh_cdiv(Cout, 64);
+  const int tiles_c = fh_cdiv(cpad, 64);
+  if (algo == 1) {
+    // halo-staged kernel: one staging of dy and of an x halo tile serves
+    // all KH*KW taps; same partials layout, same reduce
+    const int N = (int)(Mtot / ((long)HH * WW));
+    // false: the plan admitted a shape the kernel refuses, a bug the
+    // caller reports, not a fall-back case
+    return flowhip_conv_wrw_halo_launch(dy, x, x2, partials, biasp, zpage, N,
+                                        HH, WW, ld_x, ld_x2, C1, Cin, Cout,
+                                        cpad, KH, KW, nchunk, accumulate,
+                                        stream);
+  }
+  // (a KW=3 tap-sharing wrw variant that shared only dy and kept one x
+  // image per tap was measured SLOWER despite 3x less operand re-read:
+  // the 4-image LDS set halves occupancy — within-box A/B 41.0 vs 42.65
+  // pairs/s. The halo kernel above keeps ONE x image.)
+  dim3 grid(tiles_o * tiles_c, KH * KW, nchunk), block(CG_THREADS);
+  hipLaunchKernelGGL(conv_gemm_wrw_kernel, grid, block, 0, stream,
+                     (const __bf16*)dy, (const __bf16*)x, (const __bf16*)x2,
+                     partials, biasp, (const __bf16*)zpage, Mtot, HH, WW,
+                     srcH, srcW, sH, sW, ld_x, ld_x2, C1, Cin, Cout, cpad, KH,
+                     KW, padH, padW, tiles_o, tiles_c, nchunk,
+                     accumulate ? 1 : 0);
+  return true;
+}
+
+// Step 2, finish: sum the chunks (ascending) into dW (Cout, Cin, KH, KW)
+// and, with biasp / dbias given, into dbias (Cout). accumulate adds the
+// sums to what dW / dbias hold instead of overwriting them.
+void flowhip_conv_gemm_wrw_finish_launch(const float* partials,
+                                         const float* biasp, float* dw,
+                                         float* dbias, int Cin, int Cout,
+                                         int cpad, int KH, int KW, int nchunk,
+                                         bool accumulate,
+                                         hipStream_t stream) {
+  const int tiles_o = fh_cdiv(Cout, 64);
+  const long total = (long)Cout * Cin * KH * KW;
+  long rblocks = (total + CG_THREADS - 1) / CG_THREADS;
+  if (rblocks > 4096) rblocks = 4096;
+  hipLaunchKernelGGL(conv_gemm_wrw_reduce_kernel, dim3((int)rblocks),
+                     dim3(CG_THREADS), 0, stream, partials, dw, biasp, dbias,
+                     nchunk, KH * KW, tiles_o * 64, cpad, Cout, Cin,
+                     accumulate ? 1 : 0);
+}
+
+// One-shot weight gradient: partials (overwrite) + finish. The bias
+// partials live past the weight partials (caller sized the buffer).
 bool flowhip_conv_gemm_wrw_launch(const void* dy, const void* x,
                                   const void* x2, float* partials, float* dw,
                                   float* dbias, const void* zpage, long Mtot,
@@ -749,42 +874,16 @@ bool flowhip_conv_gemm_wrw_launch(const void* dy, const void* x,
                                   int padH, int padW, int nchunk, int algo,
                                   hipStream_t stream) {
   const int tiles_o = fh_cdiv(Cout, 64);
-  const int tiles_c = fh_cdiv(cpad, 64);
-  // bias partials live past the weight partials (caller sized the buffer)
   float* biasp = dbias
       ? partials + (long)nchunk * KH * KW * tiles_o * 64 * cpad
       : nullptr;
-  dim3 block(CG_THREADS);
-  if (algo == 1) {
-    // halo-staged kernel: one staging of dy and of an x halo tile serves
-    // all KH*KW taps; same partials layout, same reduce
-    const int N = (int)(Mtot / ((long)HH * WW));
-    if (!flowhip_conv_wrw_halo_launch(dy, x, x2, partials, biasp, zpage, N,
-                                      HH, WW, ld_x, ld_x2, C1, Cin, Cout,
-                                      cpad, KH, KW, nchunk, stream))
-      // the plan admitted a shape the kernel refuses: a bug the caller
-      // reports, not a fall-back case
-      return false;
-  } else {
-    // (a KW=3 tap-sharing wrw variant that shared only dy and kept one x
-    // image per tap was measured SLOWER despite 3x less operand re-read:
-    // the 4-image LDS set halves occupancy — within-box A/B 41.0 vs 42.65
-    // pairs/s. The halo kernel above keeps ONE x image.)
-    dim3 grid(tiles_o * tiles_c, KH * KW, nchunk);
-    hipLaunchKernelGGL(conv_gemm_wrw_kernel, grid, block, 0, stream,
-                       (const __bf16*)dy, (const __bf16*)x,
-                       (const __bf16*)x2, partials, biasp,
-                       (const __bf16*)zpage,
-                       Mtot, HH, WW, srcH, srcW, sH, sW, ld_x, ld_x2, C1,
-                       Cin, Cout, cpad, KH, KW, padH, padW, tiles_o, tiles_c,
-                       nchunk);
-  }
-  const long total = (long)Cout * Cin * KH * KW;
-  long rblocks = (total + CG_THREADS - 1) / CG_THREADS;
-  if (rblocks > 4096) rblocks = 4096;
-  hipLaunchKernelGGL(conv_gemm_wrw_reduce_kernel, dim3((int)rblocks), block,
-                     0, stream, partials, dw, biasp, dbias, nchunk, KH * KW,
-                     tiles_o * 64, cpad, Cout, Cin);
+  if (!flowhip_conv_gemm_wrw_partials_launch(
+          dy, x, x2, partials, biasp, zpage, Mtot, HH, WW, srcH, srcW, sH, sW,
+          ld_x, ld_x2, C1, Cin, Cout, cpad, KH, KW, padH, padW, nchunk, algo,
+          false, stream))
+    return false;
+  flowhip_conv_gemm_wrw_finish_launch(partials, biasp, dw, dbias, Cin, Cout,
+                                      cpad, KH, KW, nchunk, false, stream);
   return true;
 }
 

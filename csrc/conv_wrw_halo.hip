@@ -76,7 +76,7 @@ __global__ __launch_bounds__(WH_THREADS) void conv_wrw_halo_kernel(
     float* __restrict__ biasp,      // (nchunk, tiles_o*64) or nullptr
     const __bf16* __restrict__ zpage,
     int N, int H, int W, int ld_x, int ld_x2, int C1, int Cin, int Cout,
-    int cpad, int tiles_o, int ntx, int nty, int nchunk) {
+    int cpad, int tiles_o, int ntx, int nty, int nchunk, int accumulate) {
   constexpr int KYX = KH * KW;
   constexpr int LW = (WH_TW + KW - 1 + 7) / 8 * 8;
   constexpr int XP = (WH_TH + KH - 1) * LW * 8;
@@ -232,7 +232,9 @@ __global__ __launch_bounds__(WH_THREADS) void conv_wrw_halo_kernel(
     cur ^= 1;
   }
 
-  // partial tile: partials[chunk][tap][o0 + ..][c0 + wave*16 + ..]
+  // partial tile: partials[chunk][tap][o0 + ..][c0 + wave*16 + ..].
+  // accumulate: add to the slot this thread alone owns (see the generic
+  // kernel's epilogue) instead of overwriting it
   const int orows = tiles_o * 64;
   const int fcol = lane & 15;
   const int frow0 = (lane >> 4) * 4;
@@ -245,7 +247,9 @@ __global__ __launch_bounds__(WH_THREADS) void conv_wrw_halo_kernel(
       for (int rr = 0; rr < 4; ++rr) {
         const int o = o0 + i * 16 + frow0 + rr;
         const int c = c0 + wave * 16 + fcol;
-        pbase[(long)o * cpad + c] = acc[tap][i][rr];
+        float v = acc[tap][i][rr];
+        if (accumulate) v += pbase[(long)o * cpad + c];
+        pbase[(long)o * cpad + c] = v;
       }
   }
 
@@ -257,7 +261,11 @@ __global__ __launch_bounds__(WH_THREADS) void conv_wrw_halo_kernel(
       float s = bacc[i];
       s += __shfl_xor(s, 16, 64);
       s += __shfl_xor(s, 32, 64);
-      if (lane < 16) biasp[(long)chunk * orows + o0 + i * 16 + lane] = s;
+      if (lane < 16) {
+        float* bp = biasp + (long)chunk * orows + o0 + i * 16 + lane;
+        if (accumulate) s += *bp;
+        *bp = s;
+      }
     }
   }
 }
@@ -269,7 +277,8 @@ bool flowhip_conv_wrw_halo_launch(const void* dy, const void* x,
                                   float* biasp, const void* zpage, int N,
                                   int H, int W, int ld_x, int ld_x2, int C1,
                                   int Cin, int Cout, int cpad, int KH, int KW,
-                                  int nchunk, hipStream_t stream) {
+                                  int nchunk, bool accumulate,
+                                  hipStream_t stream) {
   if (cpad % 64 != 0 || Cout % 8 != 0) return false;
   if (x2 != nullptr && C1 % 64 != 0) return false;
   const int tiles_o = fh_cdiv(Cout, 64), tiles_c = cpad / 64;
@@ -286,7 +295,8 @@ bool flowhip_conv_wrw_halo_launch(const void* dy, const void* x,
                        stream, (const __bf16*)dy, (const __bf16*)x,          \
                        (const __bf16*)x2, partials, biasp,                   \
                        (const __bf16*)zpage, N, H, W, ld_x, ld_x2, C1, Cin,  \
-                       Cout, cpad, tiles_o, ntx, nty, nchunk);               \
+                       Cout, cpad, tiles_o, ntx, nty, nchunk,                \
+                       accumulate ? 1 : 0);                                  \
     return true;                                                             \
   }
   WH_LAUNCH(3, 3) WH_LAUNCH(1, 5) WH_LAUNCH(5, 1)

@@ -12,6 +12,7 @@ import torch.nn as nn
 from ..nn.corr import AlternateCorrBlock, CorrBlock
 from ..nn.extractor import BasicEncoder, SmallEncoder
 from ..nn.update import BasicUpdateBlock, SmallUpdateBlock
+from ..ops.functional_conv import wrw_accumulate_scope
 from ..utils.amp import autocast_ctx, autocast_off_ctx
 from ..utils.geometry import coords_grid, upflow8
 from .. import ops
@@ -107,24 +108,28 @@ class RAFT(nn.Module):
 
             flow_predictions = []
             flow_up = None
-            for _ in range(iters):
-                coords1 = coords1.detach()
-                with autocast_off_ctx(image1):
-                    corr = corr_fn(coords1)
+            # the loop's convs run `iters` times on the same weights: inside
+            # the scope each sums its weight gradients in one partials
+            # buffer and reduces once per backward pass
+            with wrw_accumulate_scope():
+                for _ in range(iters):
+                    coords1 = coords1.detach()
+                    with autocast_off_ctx(image1):
+                        corr = corr_fn(coords1)
 
-                flow = coords1 - coords0
-                net, up_mask, delta_flow = self.update_block(net, inp, corr,
-                                                             flow)
+                    flow = coords1 - coords0
+                    net, up_mask, delta_flow = self.update_block(
+                        net, inp, corr, flow)
 
-                coords1 = coords1 + delta_flow.float()
+                    coords1 = coords1 + delta_flow.float()
 
-                with autocast_off_ctx(image1):
-                    if up_mask is None:
-                        flow_up = upflow8(coords1 - coords0)
-                    else:
-                        flow_up = self.upsample_flow(
-                            (coords1 - coords0).float(), up_mask.float())
-                flow_predictions.append(flow_up)
+                    with autocast_off_ctx(image1):
+                        if up_mask is None:
+                            flow_up = upflow8(coords1 - coords0)
+                        else:
+                            flow_up = self.upsample_flow(
+                                (coords1 - coords0).float(), up_mask.float())
+                    flow_predictions.append(flow_up)
 
         if test_mode:
             return coords1 - coords0, flow_up

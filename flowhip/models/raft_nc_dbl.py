@@ -13,6 +13,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..nn.upsampler import get_upsampler
+from ..ops.functional_conv import wrw_accumulate_scope
 from ..utils.amp import autocast_ctx, autocast_off_ctx
 from .raft import RAFT as _RAFTBase
 
@@ -63,23 +64,28 @@ class RAFT_NC_DBL(_RAFTBase):
 
             flow_predictions = []
             flow_up = None
-            for _ in range(iters):
-                coords1 = coords1.detach()
-                with autocast_off_ctx(image1):
-                    corr = corr_fn(coords1)
+            # the loop's convs run `iters` times on the same weights: inside
+            # the scope each sums its weight gradients in one partials
+            # buffer and reduces once per backward pass
+            with wrw_accumulate_scope():
+                for _ in range(iters):
+                    coords1 = coords1.detach()
+                    with autocast_off_ctx(image1):
+                        corr = corr_fn(coords1)
 
-                flow = coords1 - coords0
-                net, _, delta_flow = self.update_block(net, inp, corr, flow)
+                    flow = coords1 - coords0
+                    net, _, delta_flow = self.update_block(
+                        net, inp, corr, flow)
 
-                coords1 = coords1 + delta_flow.float()
+                    coords1 = coords1 + delta_flow.float()
 
-                # NCUP upsample every iteration, guided by the GRU hidden
-                # state; x8 applied to the upsampled field (ref :161).
-                # fp32 island: the upsampler runs fp32 as in the reference.
-                with autocast_off_ctx(image1):
-                    flow_up = 8 * self.upsample_flow(
-                        (coords1 - coords0).float(), net.float())
-                flow_predictions.append(flow_up)
+                    # NCUP upsample every iteration, guided by the GRU hidden
+                    # state; x8 applied to the upsampled field (ref :161).
+                    # fp32 island: the upsampler runs fp32 as in the reference.
+                    with autocast_off_ctx(image1):
+                        flow_up = 8 * self.upsample_flow(
+                            (coords1 - coords0).float(), net.float())
+                    flow_predictions.append(flow_up)
 
         if test_mode:
             return coords1 - coords0, flow_up

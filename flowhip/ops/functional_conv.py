@@ -9,8 +9,20 @@ cached per weight version so they are rebuilt only after optimizer steps.
   forward:   out = conv(x, w) + b          (one kernel)
   bwd-data:  dx  = conv(dy, flipT(w))      (same kernel, swapped packing)
   bwd-wrw:   dW  = split-M MFMA partials + reduce (fp32)
-  bwd-bias:  dy.sum((0,2,3))               (torch reduce)
+  bwd-bias:  per-chunk column sums from the same partials kernel
+
+Inside wrw_accumulate_scope() (the models open it around the refinement
+loop) a conv that is called K times with the same weights sums its K weight
+gradients natively and hands the parameter ONE gradient, from the backward
+of a sink node placed between the parameter and its K uses (WrwSinkFn):
+in one partials buffer reduced once where that measured faster, else by a
+reduce that adds into the running dW (_wrw; the rule sits next to the plan
+code in csrc/conv_gemm.hip).
 """
+
+import contextlib
+import os
+import threading
 
 import torch
 import torch.nn.functional as F
@@ -20,6 +32,12 @@ from . import _ext
 
 def _pad64(n):
     return (n + 63) // 64 * 64
+
+
+def _pad_x8(x, pad):
+    z = x.new_zeros(x.shape[0], pad, x.shape[2], x.shape[3]).contiguous(
+        memory_format=torch.channels_last)
+    return torch.cat([x, z], dim=1)
 
 
 def _pad_c8(x, weight):
@@ -32,8 +50,7 @@ def _pad_c8(x, weight):
     pad = (-I) % 8
     if pad == 0:
         return x, weight
-    z = x.new_zeros(x.shape[0], pad, x.shape[2], x.shape[3])         .contiguous(memory_format=torch.channels_last)
-    xp = torch.cat([x, z], dim=1)
+    xp = _pad_x8(x, pad)
     wz = weight.new_zeros(O, pad, KH, KW)
     wp = torch.cat([weight, wz], dim=1)
     return xp, wp
@@ -82,12 +99,170 @@ def _packs(weight, cache, key=None):
     return cache["fwd"], cache["bwd"]
 
 
+# ---------------------------------------------------------------------------
+# Shared weight gradients: one partials buffer per weight and backward pass
+# ---------------------------------------------------------------------------
+_tls = threading.local()
+
+
+def wrw_accum_enabled():
+    """FLOWHIP_WRW_ACCUM=0 keeps every conv on the one-shot weight-gradient
+    path (A/B switch; default on)."""
+    return os.environ.get("FLOWHIP_WRW_ACCUM", "1") != "0"
+
+
+@contextlib.contextmanager
+def wrw_accumulate_scope():
+    """Convs called inside the scope with grad enabled share one weight
+    handle per conv (created at its first call). A no-op off-GPU, under
+    no_grad and for weights that need no gradient: no handle is made."""
+    if not wrw_accum_enabled():
+        yield
+        return
+    prev = getattr(_tls, "handles", None)
+    _tls.handles = {}
+    try:
+        yield
+    finally:
+        _tls.handles = prev
+
+
+class _WrwHandle:
+    """State shared by the backward calls of one weight's uses."""
+
+    __slots__ = ("buf", "live", "plan", "geom", "dw", "db")
+
+    def __init__(self):
+        self.buf = None    # partials buffer, kept until the sink runs
+        self.live = False  # buf holds the summed partials of earlier calls
+        self.plan = None   # (path, nchunk, numel, accumulate) buf is for
+        self.geom = None   # (Cout padded to 8, Cin, KH, KW, has_bias)
+        self.dw = None     # running sums of the calls already reduced,
+        self.db = None     # over the padded Cout
+
+
+class WrwSinkFn(torch.autograd.Function):
+    """Identity on (weight, bias) whose backward finishes the handle.
+
+    The convs in the scope take the sink's outputs, so by graph order the
+    sink's backward runs after the backward of every use. Those leave
+    their gradients in the handle (_wrw) and return None for weight and
+    bias; here a live partials buffer is reduced, once, and everything is
+    released. A gradient that reaches the outputs by an ordinary route is
+    added."""
+
+    @staticmethod
+    def forward(ctx, handle, weight, bias):
+        ctx.set_materialize_grads(False)
+        ctx.handle = handle
+        ctx.O = weight.shape[0]
+        if bias is None:
+            return weight.view_as(weight), None
+        return weight.view_as(weight), bias.view_as(bias)
+
+    @staticmethod
+    def backward(ctx, gw, gb):
+        h = ctx.handle
+        dw, db = h.dw, h.db
+        if h.live:
+            Op, Cin, KH, KW, has_bias = h.geom
+            dw, db = _ext.ext().conv_gemm_wrw_finish(
+                h.buf, Op, Cin, KH, KW, has_bias, h.plan[1], dw,
+                db if has_bias else None)
+            if not has_bias:
+                db = None
+        h.buf = h.dw = h.db = None
+        h.live = False
+        if dw is not None:
+            dw = dw[:ctx.O]
+            if db is not None:
+                db = db[:ctx.O]
+        if gw is not None:
+            dw = gw if dw is None else dw + gw
+        if gb is not None:
+            db = gb if db is None else db + gb
+        return None, dw, db
+
+
+def _scope_entry(cache, key, weight, bias, pad8=False):
+    """(handle, weight view, bias view) of this conv in the open scope,
+    made at the conv's first call; None outside a scope, under no_grad or
+    when neither tensor needs a gradient. `weight` may be a callable that
+    builds the tensor to differentiate (the packed z+r pair), run once."""
+    handles = getattr(_tls, "handles", None)
+    if handles is None or not torch.is_grad_enabled():
+        return None
+    k = (id(cache), key, pad8)
+    ent = handles.get(k)
+    if ent is None:
+        if callable(weight):
+            weight, bias = weight()
+        if pad8:
+            # the 8-padded weight is what the Function differentiates: the
+            # zero-column cat and its backward run once per scope
+            O, I, KH, KW = weight.shape
+            weight = torch.cat(
+                [weight, weight.new_zeros(O, (-I) % 8, KH, KW)], dim=1)
+        if not (weight.requires_grad
+                or (bias is not None and bias.requires_grad)):
+            ent = False
+        else:
+            h = _WrwHandle()
+            wh, bh = WrwSinkFn.apply(h, weight, bias)
+            ent = (h, wh, bh)
+        handles[k] = ent
+    return ent or None
+
+
+def _wrw(handle, dyp, x, x2, KH, KW, sH, sW, has_bias, O_real):
+    """Weight / bias gradient of one conv call -> (dw, dbias). With a
+    handle the gradient stays in the handle and both are None: the sink
+    returns the sum over the calls. Where the plan says accumulation wins,
+    the call's partials are summed into the handle's buffer and the sink
+    reduces once; elsewhere the call's reduce adds to the running dW, which
+    saves autograd's add launches only."""
+    E = _ext.ext()
+    if handle is None:
+        dw, db = E.conv_gemm_wrw(dyp, x, x2, KH, KW, sH, sW, has_bias)
+        if dw.shape[0] != O_real:
+            dw = dw[:O_real].contiguous()
+        return dw, (db[:O_real] if has_bias else None)
+    h = handle
+    plan = tuple(E.conv_gemm_wrw_plan(dyp, x, x2, KH, KW, sH, sW, has_bias))
+    Cin = x.shape[1] + (x2.shape[1] if x2 is not None else 0)
+    geom = (dyp.shape[1], Cin, KH, KW, has_bias)
+    if h.buf is None:
+        h.buf = torch.empty(plan[2], dtype=torch.float32, device=x.device)
+        h.plan, h.geom = plan, geom
+    if (plan, geom) != (h.plan, h.geom):
+        # another resolution than the buffer was planned for: one-shot
+        dw, db = E.conv_gemm_wrw(dyp, x, x2, KH, KW, sH, sW, has_bias)
+        h.dw = dw if h.dw is None else h.dw + dw
+        if has_bias:
+            h.db = db if h.db is None else h.db + db
+        return None, None
+    path, nchunk, _, accumulate = plan
+    E.conv_gemm_wrw_partials(dyp, x, x2, h.buf, KH, KW, sH, sW, has_bias,
+                             h.live, path, nchunk)
+    if accumulate:
+        h.live = True
+    else:
+        dw, db = E.conv_gemm_wrw_finish(h.buf, geom[0], Cin, KH, KW,
+                                        has_bias, nchunk, h.dw,
+                                        h.db if has_bias else None)
+        h.dw = dw
+        if has_bias:
+            h.db = db
+    return None, None
+
+
 class ConvGemmFn(torch.autograd.Function):
     """Stride-1 (sH=sW=1) or strided (smode 1 fwd / smode 2 bwd-data)
     same-padding conv on the MFMA kernel."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, wpk_fwd, wpk_bwd, sH, sW):
+    def forward(ctx, x, weight, bias, wpk_fwd, wpk_bwd, sH, sW,
+                handle=None):
         O, I, KH, KW = weight.shape
         b = bias.detach().float().contiguous() if bias is not None else None
         if sH == 1 and sW == 1:
@@ -97,6 +272,7 @@ class ConvGemmFn(torch.autograd.Function):
                                             0, 0, sH, sW, 1)[0]
         ctx.save_for_backward(x, wpk_bwd)
         ctx.meta = (O, I, KH, KW, bias is not None, sH, sW)
+        ctx.handle = handle
         return out
 
     @staticmethod
@@ -116,12 +292,11 @@ class ConvGemmFn(torch.autograd.Function):
                 dx = _ext.ext().conv_gemm_fwd2(dyp, None, wpk_bwd, None, I,
                                                KH, KW, 0, 0, sH, sW, 2,
                                                x.shape[2], x.shape[3])[0]
-        dw, db = _ext.ext().conv_gemm_wrw(dyp, x, None, KH, KW, sH, sW,
-                                          has_bias)
-        if dw.shape[0] != O_real:
-            dw = dw[:O_real].contiguous()
-        dbias = db[:O_real] if has_bias else None
-        return dx, dw, dbias, None, None, None, None
+        dw = dbias = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            dw, dbias = _wrw(ctx.handle, dyp, x, None, KH, KW, sH, sW,
+                             has_bias, O_real)
+        return dx, dw, dbias, None, None, None, None, None
 
 
 def can_fuse_conv(x, weight, stride, padding, dilation, groups):
@@ -168,17 +343,25 @@ def fused_conv2d(x, weight, bias, stride, padding, dilation, groups, cache,
     if can_fuse_conv(x, weight, stride, padding, dilation, groups):
         if key is None:
             key = (weight._version, weight.data_ptr())
-        if weight.shape[1] % 8 != 0 and x.stride(3) == x.size(1):
-            # ragged Cin on a tight row: pad both (16-B staging tail).
-            # A channel-narrowed view with padded ld (the corr-lookup
-            # output) needs NO pad — its tail bytes are in-row and the
-            # packed weight's zero columns null them (saves a full-tensor
-            # cat copy per GRU iteration).
+        # ragged Cin on a tight row: pad both (16-B staging tail).
+        # A channel-narrowed view with padded ld (the corr-lookup
+        # output) needs NO pad — its tail bytes are in-row and the
+        # packed weight's zero columns null them (saves a full-tensor
+        # cat copy per GRU iteration).
+        pad8 = weight.shape[1] % 8 != 0 and x.stride(3) == x.size(1)
+        ent = _scope_entry(cache, key, weight, bias, pad8)
+        handle = None
+        if ent is not None:
+            handle, wh, bias = ent
+            if pad8:
+                x = _pad_x8(x, (-weight.shape[1]) % 8)
+            weight = wh
+        elif pad8:
             x, weight = _pad_c8(x, weight)
         wf, wb = _packs(weight, cache, key)
         from torch.nn.modules.utils import _pair
         sH, sW = _pair(stride)
-        return ConvGemmFn.apply(x, weight, bias, wf, wb, sH, sW)
+        return ConvGemmFn.apply(x, weight, bias, wf, wb, sH, sW, handle)
     import os
     if x.is_cuda and os.environ.get("FLOWHIP_LOG_FALLBACK", "0") == "1":
         print(f"[conv fallback] w={tuple(weight.shape)} stride={stride} "
@@ -194,13 +377,14 @@ class ConvGemmCat2Fn(torch.autograd.Function):
     (4 per GRU iteration). x1's channel count must be a multiple of 64."""
 
     @staticmethod
-    def forward(ctx, x1, x2, weight, bias, wpk_fwd, wpk_bwd):
+    def forward(ctx, x1, x2, weight, bias, wpk_fwd, wpk_bwd, handle=None):
         O, I, KH, KW = weight.shape
         b = bias.detach().float().contiguous() if bias is not None else None
         out = _ext.ext().conv_gemm_fwd2(x1, x2, wpk_fwd, b, O, KH, KW, 0,
                                         0)[0]
         ctx.save_for_backward(x1, x2, wpk_bwd)
         ctx.meta = (O, I, KH, KW, bias is not None, x1.shape[1])
+        ctx.handle = handle
         return out
 
     @staticmethod
@@ -213,12 +397,11 @@ class ConvGemmCat2Fn(torch.autograd.Function):
         dyp, O_real = _pad_dy8(dy)
         dx1, dx2 = _ext.ext().conv_gemm_fwd2(dyp, None, wpk_bwd, None, I, KH,
                                              KW, C1, 0)
-        dw, db = _ext.ext().conv_gemm_wrw(dyp, x1, x2, KH, KW, 1, 1,
-                                          has_bias)
-        if dw.shape[0] != O_real:
-            dw = dw[:O_real].contiguous()
-        dbias = db[:O_real] if has_bias else None
-        return dx1, dx2, dw, dbias, None, None
+        dw = dbias = None
+        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
+            dw, dbias = _wrw(ctx.handle, dyp, x1, x2, KH, KW, 1, 1,
+                             has_bias, O_real)
+        return dx1, dx2, dw, dbias, None, None, None
 
 
 class ConvGemmCat2ZrFn(torch.autograd.Function):
@@ -249,6 +432,8 @@ class ConvGemmCat2ZrFn(torch.autograd.Function):
             dy = dy.to(torch.bfloat16)
         dx1, dx2 = _ext.ext().conv_gemm_fwd2(dy, None, wpk_bwd, None, I, KH,
                                              KW, C1, 0)
+        if not any(ctx.needs_input_grad[2:6]):
+            return dx1, dx2, None, None, None, None, None, None, None
         dw, db = _ext.ext().conv_gemm_wrw(dy, x1, x2, KH, KW, 1, 1, True)
         return (dx1, dx2, dw[:Oz], dw[Oz:].contiguous(), db[:Oz],
                 db[Oz:].contiguous(), None, None, None)
@@ -278,6 +463,16 @@ def fused_gru_zr_conv(h, x, convz, convr, padding, cache):
                 cache["bwd"] = _pack_bwd(w)
                 cache["bias"] = torch.cat([convz.bias, convr.bias]) \
                     .float().contiguous()
+        ent = _scope_entry(cache, key, lambda: (
+            torch.cat([convz.weight, convr.weight]),
+            torch.cat([convz.bias, convr.bias])), None)
+        if ent is not None:
+            # the packed pair is what the Function differentiates: one
+            # weight cat (and its backward slices) per scope, and the two
+            # gates' gradients share one partials buffer
+            handle, wh, bh = ent
+            return ConvGemmCat2Fn.apply(h, x, wh, bh, cache["fwd"],
+                                        cache["bwd"], handle)
         return ConvGemmCat2ZrFn.apply(h, x, convz.weight, convr.weight,
                                       convz.bias, convr.bias, cache["bias"],
                                       cache["fwd"], cache["bwd"])
@@ -305,6 +500,10 @@ def fused_conv2d_cat2(x1, x2, weight, bias, padding, cache, key):
     from torch.nn.modules.utils import _pair
     if fusable and _pair(padding) == (KH // 2, KW // 2):
         wf, wb = _packs(weight, cache, key)
+        ent = _scope_entry(cache, key, weight, bias)
+        if ent is not None:
+            handle, wh, bh = ent
+            return ConvGemmCat2Fn.apply(x1, x2, wh, bh, wf, wb, handle)
         return ConvGemmCat2Fn.apply(x1, x2, weight, bias, wf, wb)
     import os
     if x1.is_cuda and os.environ.get("FLOWHIP_LOG_FALLBACK", "0") == "1":
