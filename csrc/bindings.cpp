@@ -138,6 +138,11 @@ void flowhip_zero_inject_bwd_launch(const float* gout, float* dinp,
                                     long total, int ih, int iw, int oh,
                                     int ow, int sH, int sW,
                                     hipStream_t stream);
+void flowhip_forward_splat_plan(int H, int W, int splits, int* chunk_out,
+                                int* G_out);
+void flowhip_forward_splat_launch(const float* flow, float* out, double* ws_d,
+                                  int* ws_i, int B, int H, int W, int chunk,
+                                  int G, hipStream_t stream);
 void flowhip_gru_gate1_fwd_launch(const void* zr, const void* h, void* z,
                                   void* rh, long total, int C, long P,
                                   int is_bf16, int cl, hipStream_t stream);
@@ -942,6 +947,60 @@ torch::Tensor zero_inject_bwd(torch::Tensor gout, int64_t sH, int64_t sW,
                                  dinp.numel(), (int)ih, (int)iw, oh, ow,
                                  (int)sH, (int)sW, stream);
   return dinp;
+}
+
+// The search kernel indexes targets and sources with int and overshoots the
+// last tile by up to one tile of targets.
+static void forward_splat_check_hw(int64_t H, int64_t W) {
+  TORCH_CHECK(H >= 1 && W >= 1 && H * W < (int64_t(1) << 31) - 4096,
+              "forward_splat: H*W must stay below 2^31");
+}
+
+// Chunk count G the splat picks for an (H, W) field (splits = 0), or the one
+// a forced `splits` comes to once no chunk is left empty.
+int64_t forward_splat_plan(int64_t H, int64_t W, int64_t splits) {
+  forward_splat_check_hw(H, W);
+  TORCH_CHECK(splits >= 0, "forward_splat: splits must be >= 0 (0 = planned)");
+  int chunk, G;
+  flowhip_forward_splat_plan((int)H, (int)W,
+                             (int)std::min<int64_t>(splits, H * W), &chunk,
+                             &G);
+  return G;
+}
+
+// Nearest-neighbour forward splat, (B,2,H,W) fp32 -> (B,2,H,W) fp32.
+// splits: 0 = planned chunk count, otherwise forced (1 = single pass that
+// writes the output directly, > 1 = partials + finish kernel).
+torch::Tensor forward_splat(torch::Tensor flow, int64_t splits) {
+  TORCH_CHECK(flow.is_cuda() && flow.dtype() == torch::kFloat32 &&
+                  flow.dim() == 4 && flow.size(1) == 2,
+              "forward_splat: (B,2,H,W) fp32 CUDA tensor required");
+  TORCH_CHECK(splits >= 0, "forward_splat: splits must be >= 0 (0 = planned)");
+  auto x = flow.contiguous();
+  const int64_t B = x.size(0), H = x.size(2), W = x.size(3);
+  auto out = torch::empty_like(x);
+  if (B == 0 || H == 0 || W == 0) return out;
+  forward_splat_check_hw(H, W);
+  TORCH_CHECK(B <= 65535, "forward_splat: batch exceeds the grid limit");
+  int chunk, G;
+  flowhip_forward_splat_plan((int)H, (int)W,
+                             (int)std::min<int64_t>(splits, H * W), &chunk,
+                             &G);
+  torch::Tensor ws_d, ws_i;
+  if (G > 1) {
+    ws_d = torch::empty({B, (int64_t)G, H * W},
+                        x.options().dtype(torch::kFloat64));
+    ws_i = torch::empty({B, (int64_t)G, H * W},
+                        x.options().dtype(torch::kInt32));
+  }
+  const c10::cuda::CUDAGuard guard(x.device());
+  hipStream_t stream = at::cuda::getCurrentCUDAStream().stream();
+  flowhip_forward_splat_launch(
+      x.data_ptr<float>(), out.data_ptr<float>(),
+      G > 1 ? ws_d.data_ptr<double>() : nullptr,
+      G > 1 ? ws_i.data_ptr<int>() : nullptr, (int)B, (int)H, (int)W, chunk,
+      G, stream);
+  return out;
 }
 
 std::vector<torch::Tensor> instnorm_cl_fwd(torch::Tensor x, double eps) {
@@ -1823,6 +1882,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "channels-last InstanceNorm2d backward");
   m.def("zero_inject_fwd", &zero_inject_fwd, "sparse injection scatter");
   m.def("zero_inject_bwd", &zero_inject_bwd, "backward gather of inject");
+  m.def("forward_splat", &forward_splat,
+        "nearest-neighbour forward splat of a flow field (warm start); "
+        "splits: 0 = planned source chunks, n = forced",
+        py::arg("flow"), py::arg("splits") = 0);
+  m.def("forward_splat_plan", &forward_splat_plan,
+        "source chunk count G the splat uses for an (H, W) field",
+        py::arg("H"), py::arg("W"), py::arg("splits") = 0);
   m.def("gru_gate1_fwd", &gru_gate1_fwd, "fused GRU z/r gates + r*h");
   m.def("gru_gate1_bwd", &gru_gate1_bwd, "backward of gru_gate1");
   m.def("gru_gate2_fwd", &gru_gate2_fwd, "fused GRU tanh + lerp update");

@@ -7,6 +7,7 @@ As in the reference, --model is the CHECKPOINT path; the architecture is
 selected with --arch (reference hardcoded RAFT).
 
     python demo.py --model ckpt.pth --path frames_dir [--out demo_out]
+                   [--warm_start]
 """
 
 import argparse
@@ -20,6 +21,7 @@ from PIL import Image
 from flowhip.config import add_ncup_module_flags, finalize_args
 from flowhip.data import flow_viz
 from flowhip.engine import checkpoints
+from flowhip.engine.stream import FlowStream
 from flowhip.models import build_model
 from flowhip.utils.geometry import InputPadder
 from flowhip.utils.geometry import InputPadder
@@ -63,10 +65,13 @@ def demo(args):
                        + glob.glob(os.path.join(args.path, "*.jpg")))
         images = [load_image(f) for f in files]
 
+        # --warm_start: the frames are one sequence; each pair starts from
+        # the previous pair's flow, splatted forward on the device
+        stream = FlowStream(model, iters=20, warm_start=args.warm_start)
         for i, (image1, image2) in enumerate(zip(images[:-1], images[1:])):
             padder = InputPadder(image1.shape)
             image1, image2 = padder.pad(image1, image2)
-            flow_low, flow_up = model(image1, image2, iters=20, test_mode=True)
+            flow_low, flow_up = stream.step(image1, image2)
             viz(image1, flow_up, os.path.join(args.out, "flow_%04d.png" % i))
 
 
@@ -81,6 +86,10 @@ def build_parser():
     parser.add_argument("--alternate_corr", action="store_true",
                         help="on-demand correlation lookup (no all-pairs "
                         "volume; for frames larger than memory allows)")
+    parser.add_argument("--warm_start", action="store_true",
+                        help="treat the frames as one sequence: start each "
+                        "pair from the previous pair's flow (device-side "
+                        "nearest splat)")
     add_ncup_module_flags(parser)
     return parser
 

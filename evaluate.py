@@ -41,7 +41,9 @@ if __name__ == "__main__":
         elif args.dataset == "sintel_submission":
             # the reference ships these as commented-out lines the user must
             # edit in (evaluate.py:267,271); defined behavior: CLI choices
-            create_sintel_submission(model, warm_start=True)
+            create_sintel_submission(
+                model, warm_start=True,
+                splat="device" if args.device_warm_start else "scipy")
         elif args.dataset == "kitti_submission":
             create_kitti_submission(model)
         else:

@@ -242,6 +242,10 @@ def build_eval_parser(argv=None):
     parser.add_argument("--alternate_corr", action="store_true",
                         help="on-demand correlation lookup (no all-pairs "
                         "volume; memory-bounded, for large frames)")
+    parser.add_argument("--device_warm_start", action="store_true",
+                        help="sintel_submission: forward-warp the previous "
+                        "flow on the device (ops.forward_splat) instead of "
+                        "through scipy on the host")
 
     add_ncup_module_flags(parser, argv=argv)
     return parser

@@ -1,1 +1,1 @@
-from . import checkpoints, distributed, evaluate, logger, train  # noqa: F401
+from . import checkpoints, distributed, evaluate, logger, stream, train  # noqa: F401

@@ -11,6 +11,7 @@ import os
 import numpy as np
 import torch
 
+from .. import ops
 from ..data import datasets, flow_viz, frame_utils
 from ..utils.geometry import InputPadder, forward_interpolate
 
@@ -21,9 +22,16 @@ def _device_of(model):
 
 @torch.no_grad()
 def create_sintel_submission(model, iters=32, warm_start=False,
-                             output_path="sintel_submission", write_png=False):
+                             output_path="sintel_submission", write_png=False,
+                             splat="scipy"):
     """Write Sintel leaderboard .flo files (reference evaluate.py:23-57),
-    optionally warm-starting each sequence from the previous frame's flow."""
+    optionally warm-starting each sequence from the previous frame's flow.
+
+    splat: how the warm start forward-warps the previous flow. "scipy" is
+    the reference's host path (griddata nearest); "device" keeps it on the
+    model's device through `ops.forward_splat` — same nearest-source rule,
+    ties to the lowest source index, no host round trip."""
+    assert splat in ("scipy", "device"), splat
     model.eval()
     device = _device_of(model)
     for dstype in ["clean", "final"]:
@@ -42,7 +50,9 @@ def create_sintel_submission(model, iters=32, warm_start=False,
                                       flow_init=flow_prev, test_mode=True)
             flow = padder.unpad(flow_pr[0]).permute(1, 2, 0).cpu().numpy()
 
-            if warm_start:
+            if warm_start and splat == "device":
+                flow_prev = ops.forward_splat(flow_low)
+            elif warm_start:
                 flow_prev = forward_interpolate(flow_low[0])[None].to(device)
 
             output_dir = os.path.join(output_path, dstype, sequence)

@@ -14,6 +14,7 @@ SURVEY.md §2.2 kernel inventory):
   conf_pool(data, conf)                kernel #7  (confidence-based pooling)
   zero_inject(x, sh, sw)               kernel #8  (sparse injection scatter)
   convex_upsample(flow, mask)          kernel #11 (RAFT convex upsample)
+  forward_splat(flow)                  warm-start nearest splat (no gradient)
   sequence_loss(preds, gt, valid, g)   kernel #12 (loss; torch for now)
 """
 
@@ -195,6 +196,23 @@ def zero_inject(inp, scale_h, scale_w, out_h=None, out_w=None):
         ow = out_w if out_w is not None else inp.shape[3] * scale_w
         return ZeroInjectFn.apply(inp, scale_h, scale_w, oh, ow)
     return torch_ref.zero_inject(inp, scale_h, scale_w, out_h, out_w)
+
+
+def forward_splat(flow, splits=0):
+    """Warm-start splat: forward-warp a flow field (B,2,H,W) or (2,H,W) onto
+    the grid, each cell taking the flow of the nearest landed source
+    (reference core/utils/utils.py:28-56, scipy griddata "nearest" there).
+
+    Defined behaviour where scipy's is not: ties go to the lowest source
+    index, and a sample with no source inside the frame yields zeros. Not
+    differentiable. HIP for CUDA fp32 tensors (`splits` forces the kernel's
+    source chunk count, 0 = planned); the float64 oracle otherwise."""
+    if _ext.use_hip(flow) and flow.dtype == torch.float32:
+        from .functional_upsample import ForwardSplatFn
+        if flow.dim() == 3:
+            return ForwardSplatFn.apply(flow[None], splits)[0]
+        return ForwardSplatFn.apply(flow, splits)
+    return torch_ref.forward_splat(flow)
 
 
 def convex_upsample(flow, mask, factor=8):

@@ -41,6 +41,22 @@ class ZeroInjectFn(torch.autograd.Function):
 
 
 
+class ForwardSplatFn(torch.autograd.Function):
+    """Nearest-neighbour forward splat (csrc/forward_splat.hip; reference
+    core/utils/utils.py:28-56). A selection, not a differentiable map: the
+    output is marked non-differentiable."""
+
+    @staticmethod
+    def forward(ctx, flow, splits):
+        out = _ext.ext().forward_splat(flow.contiguous(), int(splits))
+        ctx.mark_non_differentiable(out)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        return None, None
+
+
 class AreaUp2xFn(torch.autograd.Function):
     """Exact-2x area interpolation (== nearest duplication) with a
     gather-only backward (torch's is an atomic adaptive-pool scatter)."""

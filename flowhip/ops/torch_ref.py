@@ -7,7 +7,8 @@ These serve three roles:
   3. the documentation of the exact math each kernel computes, with citations
      into the reference repo.
 
-Every function here is differentiable through torch autograd.
+Every function here is differentiable through torch autograd, except
+`forward_splat` (a nearest-source selection).
 """
 
 import math
@@ -222,6 +223,73 @@ def zero_inject(inp, scale_h, scale_w, out_h=None, out_w=None):
     out = inp.new_zeros((b, c, oh, ow))
     out[:, :, scale_h // 2::scale_h, scale_w // 2::scale_w] = inp
     return out
+
+
+# ---------------------------------------------------------------------------
+# Warm-start forward splat  (reference core/utils/utils.py:28-56)
+# ---------------------------------------------------------------------------
+
+@torch.no_grad()
+def forward_splat(flow, return_ties=False, max_pairs=1 << 22):
+    """Forward-warp a flow field onto the grid: each cell takes the flow of
+    the nearest landed source (the reference's scipy griddata "nearest").
+    A selection, so not differentiable (the one such function here).
+
+    Source i = y*W + x sits at (x + dx, y + dy), evaluated in float64 as
+    numpy does; it is valid iff 0 < px < W and 0 < py < H (NaN fails). A
+    target (tx, ty) copies the valid source with the smallest
+    (px-tx)^2 + (py-ty)^2 (float64, each op rounded on its own). Ties go to
+    the lowest source index; a sample without a valid source gives zeros
+    (scipy: unspecified / raises).
+
+    In:  (B, 2, H, W) or (2, H, W). Out: same shape and dtype, detached.
+    return_ties: also return a bool (B, H, W) / (H, W) map of the targets
+    whose minimum is attained by more than one source.
+    Chunked float64 brute force, at most `max_pairs` pairs per sample at a
+    time.
+    """
+    squeeze = flow.dim() == 3
+    fl = flow.detach()[None] if squeeze else flow.detach()
+    B, _, H, W = fl.shape
+    HW = H * W
+    dev = fl.device
+    fl = fl.reshape(B, 2, HW)
+
+    gy, gx = torch.meshgrid(
+        torch.arange(H, device=dev, dtype=torch.float64),
+        torch.arange(W, device=dev, dtype=torch.float64), indexing="ij")
+    gx, gy = gx.reshape(-1), gy.reshape(-1)
+    px = gx + fl[:, 0].double()
+    py = gy + fl[:, 1].double()
+    valid = (px > 0) & (px < W) & (py > 0) & (py < H)
+    inf = float("inf")
+    px = torch.where(valid, px, inf)[:, None, :]   # (B, 1, sources)
+    py = torch.where(valid, py, inf)[:, None, :]
+    src_idx = torch.arange(HW, device=dev)
+
+    best = torch.empty(B, HW, dtype=torch.long, device=dev)
+    found = torch.empty(B, HW, dtype=torch.bool, device=dev)
+    ties = torch.empty(B, HW, dtype=torch.bool, device=dev)
+    step = max(1, max_pairs // HW)
+    for t0 in range(0, HW, step):
+        ddx = px - gx[None, t0:t0 + step, None]    # (B, targets, sources)
+        ddy = py - gy[None, t0:t0 + step, None]
+        d = ddx * ddx + ddy * ddy
+        dmin = d.min(dim=2, keepdim=True).values
+        hit = (d == dmin) & (dmin < inf)
+        # lowest index among the sources that attain the minimum
+        best[:, t0:t0 + step] = torch.where(hit, src_idx, HW).min(dim=2).values
+        found[:, t0:t0 + step] = dmin[..., 0] < inf
+        ties[:, t0:t0 + step] = hit.sum(dim=2) > 1
+
+    idx = best.clamp(max=HW - 1)[:, None, :].expand(B, 2, HW)
+    out = torch.where(found[:, None, :], torch.gather(fl, 2, idx),
+                      torch.zeros((), dtype=fl.dtype, device=dev))
+    out = out.reshape(B, 2, H, W)
+    ties = ties.reshape(B, H, W)
+    if squeeze:
+        out, ties = out[0], ties[0]
+    return (out, ties) if return_ties else out
 
 
 # ---------------------------------------------------------------------------
