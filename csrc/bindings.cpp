@@ -8,7 +8,10 @@
 #include <c10/cuda/CUDAGuard.h>
 #include <hip/hip_runtime.h>
 
-// launchers defined in the .hip translation units
+// the conv family's geometry, plan and launchers
+#include "conv_gemm.h"
+
+// launchers defined in the other .hip translation units
 void flowhip_bgemm_nt_launch(const void* A, const void* B, void* C,
                              float alpha, int batch, int M, int N, int K,
                              int out_bf16, hipStream_t stream);
@@ -73,9 +76,6 @@ bool flowhip_nconv_wrw_tiled_launch(const float* dnomin, const float* ddenom,
                                     int Ci, int Co, int H, int W, int K,
                                     hipStream_t stream);
 int flowhip_instnorm_partial_rows(int N, int C, long P);
-void flowhip_conv_gemm_pack_launch(const float* w, void* wpk, long total,
-                                   int O, int I, int KH, int KW, int cpad,
-                                   int flip, hipStream_t stream);
 void flowhip_transpose_cast_launch(const void* in, void* out, int B, int M,
                                    int N, int in_bf16, hipStream_t stream);
 void flowhip_conf_pool_fwd_launch(const float* data, const float* conf,
@@ -87,41 +87,6 @@ void flowhip_conf_pool_bwd_launch(const float* gdata_ds,
                                   const unsigned char* code, float* gdata,
                                   float* gconf, long total_in, int H, int W,
                                   int OH, int OW, hipStream_t stream);
-void flowhip_conv_gemm_fwd_launch(const void* x, const void* x2,
-                                  const void* wpk, const float* bias,
-                                  void* out, void* out2, const void* zpage,
-                                  long Mtot, int HH, int WW, int srcH,
-                                  int srcW, int sH, int sW, int ld_x,
-                                  int ld_x2, int C1, int Cin, int Cout,
-                                  int cpad, int KH, int KW, int padH,
-                                  int padW, int osplit, int act, int smode,
-                                  hipStream_t stream);
-bool flowhip_conv_gemm_wrw_launch(const void* dy, const void* x,
-                                  const void* x2, float* partials, float* dw,
-                                  float* dbias,
-                                  const void* zpage, long Mtot, int HH,
-                                  int WW, int srcH, int srcW, int sH, int sW,
-                                  int ld_x, int ld_x2, int C1,
-                                  int Cin, int Cout, int cpad, int KH,
-                                  int KW, int padH, int padW, int nchunk,
-                                  int algo, hipStream_t stream);
-bool flowhip_conv_gemm_wrw_partials_launch(
-    const void* dy, const void* x, const void* x2, float* partials,
-    float* biasp, const void* zpage, long Mtot, int HH, int WW, int srcH,
-    int srcW, int sH, int sW, int ld_x, int ld_x2, int C1, int Cin, int Cout,
-    int cpad, int KH, int KW, int padH, int padW, int nchunk, int algo,
-    bool accumulate, hipStream_t stream);
-void flowhip_conv_gemm_wrw_finish_launch(const float* partials,
-                                         const float* biasp, float* dw,
-                                         float* dbias, int Cin, int Cout,
-                                         int cpad, int KH, int KW, int nchunk,
-                                         bool accumulate,
-                                         hipStream_t stream);
-bool flowhip_conv_gemm_wrw_accumulate_wins(int path);
-int flowhip_conv_gemm_wrw_plan(long Mtot, int HH, int WW, int srcH, int srcW,
-                               int sH, int sW, bool has_x2, int C1, int Cout,
-                               int cpad, int KH, int KW, int padH, int padW,
-                               int algo, int nchunk_req, int* nchunk_out);
 void flowhip_instnorm_cl_fwd_launch(const void* x, void* y, float* mean,
                                     float* rstd, float* partials, int N,
                                     int C, long P, float eps, int is_bf16,
@@ -1130,12 +1095,40 @@ static void cg_check_x(const torch::Tensor& x, int& ld) {
               x.stride(0) == (long)ld * x.size(3) * x.size(2));
 }
 
+// The geometry of a same-padding conv over x (and the virtually
+// concatenated x2) whose m axis walks N x OH x OW pixels of Cout channels.
+static ConvGeom cg_geom(const torch::Tensor& x,
+                        const c10::optional<torch::Tensor>& x2, int64_t Cout,
+                        int64_t OH, int64_t OW, int64_t KH, int64_t KW,
+                        int64_t sH, int64_t sW) {
+  ConvGeom g{};
+  cg_check_x(x, g.ld_x);
+  g.srcH = x.size(2); g.srcW = x.size(3);
+  g.C1 = g.Cin = x.size(1);
+  if (x2.has_value()) {
+    cg_check_x(x2.value(), g.ld_x2);
+    TORCH_CHECK(x2->size(0) == x.size(0) && x2->size(2) == g.srcH &&
+                x2->size(3) == g.srcW);
+    g.Cin += (int)x2->size(1);
+  }
+  g.cpad = cg_cpad(g.Cin);
+  g.Cout = (int)Cout; g.HH = (int)OH; g.WW = (int)OW;
+  g.Mtot = x.size(0) * OH * OW;
+  g.KH = (int)KH; g.KW = (int)KW; g.padH = g.KH / 2; g.padW = g.KW / 2;
+  g.sH = (int)sH; g.sW = (int)sW;
+  return g;
+}
+
+static const void* cg_ptr(const c10::optional<torch::Tensor>& t) {
+  return t.has_value() ? t->data_ptr() : nullptr;
+}
+
 torch::Tensor conv_gemm_pack(torch::Tensor w, bool flip) {
   TORCH_CHECK(w.is_cuda() && w.is_contiguous() &&
               w.scalar_type() == torch::kFloat32 && w.dim() == 4);
   const int O = w.size(0), I = w.size(1), KH = w.size(2), KW = w.size(3);
   const int R0 = flip ? I : O;
-  const int cpad = ((flip ? O : I) + 63) / 64 * 64;
+  const int cpad = cg_cpad(flip ? O : I);
   auto wpk = torch::empty({(long)KH * KW, (long)R0, (long)cpad},
                           w.options().dtype(torch::kBFloat16));
   const c10::cuda::CUDAGuard guard(w.device());
@@ -1151,37 +1144,28 @@ std::vector<torch::Tensor> conv_gemm_fwd2(
     c10::optional<torch::Tensor> bias, int64_t Cout, int64_t KH, int64_t KW,
     int64_t osplit, int64_t act, int64_t sH, int64_t sW, int64_t smode,
     int64_t outH, int64_t outW) {
-  int ld_x, ld_x2 = 0;
-  cg_check_x(x, ld_x);
   TORCH_CHECK(wpk.is_cuda() && wpk.is_contiguous() &&
               wpk.scalar_type() == torch::kBFloat16 && wpk.dim() == 3);
-  const int N = x.size(0), C1 = x.size(1), H = x.size(2), W = x.size(3);
-  int Cin = C1;
-  const void* x2p = nullptr;
-  if (x2.has_value()) {
-    int l2;
-    cg_check_x(x2.value(), l2);
-    TORCH_CHECK(x2->size(0) == N && x2->size(2) == H && x2->size(3) == W);
-    TORCH_CHECK(C1 % 64 == 0, "conv_gemm cat2: first input must be a "
-                "multiple of 64 channels");
-    ld_x2 = l2;
-    Cin = C1 + (int)x2->size(1);
-    x2p = x2->data_ptr();
-  }
-  const int cpad = wpk.size(2);
   TORCH_CHECK(wpk.size(0) == KH * KW && wpk.size(1) == Cout);
   TORCH_CHECK(smode >= 0 && smode <= 2 && sH >= 1 && sW >= 1);
+  TORCH_CHECK(x.dim() == 4);
   // output spatial dims: same-pad for smode 0/1; smode 2 (strided
   // transposed conv, = backward-data of smode 1) takes them explicitly
-  int OH = H, OW = W;
+  const long N = x.size(0);
+  int64_t OH = x.size(2), OW = x.size(3);
   if (smode == 1) {
-    OH = (int)((H + 2 * (KH / 2) - KH) / sH + 1);
-    OW = (int)((W + 2 * (KW / 2) - KW) / sW + 1);
+    OH = (OH + 2 * (KH / 2) - KH) / sH + 1;
+    OW = (OW + 2 * (KW / 2) - KW) / sW + 1;
   } else if (smode == 2) {
     TORCH_CHECK(outH > 0 && outW > 0, "conv_gemm smode=2 needs outH/outW");
-    OH = (int)outH; OW = (int)outW;
+    OH = outH; OW = outW;
   }
-  const long Mtot = (long)N * OH * OW;
+  ConvGeom g = cg_geom(x, x2, Cout, OH, OW, KH, KW, sH, sW);
+  TORCH_CHECK(!x2.has_value() || g.C1 % 64 == 0,
+              "conv_gemm cat2: first input must be a "
+              "multiple of 64 channels");
+  g.cpad = wpk.size(2);
+  if (smode == 0) g.sH = g.sW = 1;  // smode 0 ignores the stride arguments
   const float* bptr = nullptr;
   if (bias.has_value()) {
     TORCH_CHECK(bias->is_contiguous() &&
@@ -1192,29 +1176,23 @@ std::vector<torch::Tensor> conv_gemm_fwd2(
   const c10::cuda::CUDAGuard guard(x.device());
   hipStream_t stream = at::cuda::getCurrentCUDAStream().stream();
   if (osplit <= 0 || osplit >= Cout) {
-    auto out = torch::empty({(long)N, Cout, (long)OH, (long)OW}, x.options(),
+    auto out = torch::empty({N, Cout, OH, OW}, x.options(),
                             torch::MemoryFormat::ChannelsLast);
-    flowhip_conv_gemm_fwd_launch(x.data_ptr(), x2p, wpk.data_ptr(), bptr,
-                                 out.data_ptr(), nullptr, cg_zero_page(),
-                                 Mtot, OH, OW, H, W, (int)sH, (int)sW, ld_x,
-                                 ld_x2, C1, Cin, (int)Cout,
-                                 cpad, (int)KH, (int)KW, (int)KH / 2,
-                                 (int)KW / 2, (int)Cout, (int)act,
+    flowhip_conv_gemm_fwd_launch(x.data_ptr(), cg_ptr(x2), wpk.data_ptr(),
+                                 bptr, out.data_ptr(), nullptr,
+                                 cg_zero_page(), g, (int)Cout, (int)act,
                                  (int)smode, stream);
     return {out};
   }
   TORCH_CHECK(smode == 0, "conv_gemm: osplit only with smode 0");
-  auto out = torch::empty({(long)N, osplit, (long)H, (long)W}, x.options(),
+  auto out = torch::empty({N, osplit, OH, OW}, x.options(),
                           torch::MemoryFormat::ChannelsLast);
-  auto out2 = torch::empty({(long)N, Cout - osplit, (long)H, (long)W},
-                           x.options(), torch::MemoryFormat::ChannelsLast);
-  flowhip_conv_gemm_fwd_launch(x.data_ptr(), x2p, wpk.data_ptr(), bptr,
+  auto out2 = torch::empty({N, Cout - osplit, OH, OW}, x.options(),
+                           torch::MemoryFormat::ChannelsLast);
+  flowhip_conv_gemm_fwd_launch(x.data_ptr(), cg_ptr(x2), wpk.data_ptr(), bptr,
                                out.data_ptr(), out2.data_ptr(),
-                               cg_zero_page(), Mtot, H, W, H, W, 1, 1, ld_x,
-                               ld_x2, C1,
-                               Cin, (int)Cout, cpad, (int)KH, (int)KW,
-                               (int)KH / 2, (int)KW / 2, (int)osplit,
-                               (int)act, 0, stream);
+                               cg_zero_page(), g, (int)osplit, (int)act, 0,
+                               stream);
   return {out, out2};
 }
 
@@ -1225,114 +1203,61 @@ torch::Tensor conv_gemm_fwd(torch::Tensor x, torch::Tensor wpk,
                         act, 1, 1, 0, 0, 0)[0];
 }
 
+// Weight gradient. The one-shot conv_gemm_wrw is the three steps below in
+// one call: plan -> partials (overwrite) -> finish. Callers that sum the
+// gradients of several calls (same weights, same shapes) run the steps
+// themselves: plan -> partials (accumulate) x K -> finish.
+static ConvGeom cg_wrw_geom(const torch::Tensor& dy, const torch::Tensor& x,
+                            const c10::optional<torch::Tensor>& x2,
+                            int64_t KH, int64_t KW, int64_t sH, int64_t sW) {
+  TORCH_CHECK(dy.is_cuda() && dy.dim() == 4 &&
+              dy.scalar_type() == torch::kBFloat16 && dy.stride(1) == 1 &&
+              dy.stride(3) == dy.size(1),
+              "conv_gemm_wrw: dy must be channels-last contiguous");
+  TORCH_CHECK(x.dim() == 4 && dy.size(0) == x.size(0));
+  return cg_geom(x, x2, dy.size(1), dy.size(2), dy.size(3), KH, KW, sH, sW);
+}
+
+// path (generic per-tap | halo-staged) and its split-M chunk count
+static int cg_wrw_plan(const ConvGeom& g, int64_t algo, int64_t nchunk_req,
+                       int* nchunk) {
+  TORCH_CHECK(algo >= -1 && algo <= 1, "conv_gemm_wrw: algo must be -1, 0, 1");
+  const int path =
+      flowhip_conv_gemm_wrw_plan(g, (int)algo, (int)nchunk_req, nchunk);
+  TORCH_CHECK(path >= 0,
+              "conv_gemm_wrw: algo=1 (halo) forced on a shape outside its "
+              "envelope (stride 1, same padding, 3x3 / 1x5 / 5x1)");
+  return path;
+}
+
 std::vector<torch::Tensor> conv_gemm_wrw(torch::Tensor dy, torch::Tensor x,
                                          c10::optional<torch::Tensor> x2,
                                          int64_t KH, int64_t KW, int64_t sH,
                                          int64_t sW, bool want_bias,
                                          int64_t algo, int64_t nchunk_req) {
-  int ld_x, ld_x2 = 0;
-  cg_check_x(x, ld_x);
-  TORCH_CHECK(dy.is_cuda() && dy.scalar_type() == torch::kBFloat16 &&
-              dy.stride(1) == 1 && dy.stride(3) == dy.size(1),
-              "conv_gemm_wrw: dy must be channels-last contiguous");
-  const int N = x.size(0), C1 = x.size(1), H = x.size(2), W = x.size(3);
-  const int OH = dy.size(2), OW = dy.size(3);
-  TORCH_CHECK(dy.size(0) == N);
-  int Cin = C1;
-  const void* x2p = nullptr;
-  if (x2.has_value()) {
-    int l2;
-    cg_check_x(x2.value(), l2);
-    ld_x2 = l2;
-    Cin = C1 + (int)x2->size(1);
-    x2p = x2->data_ptr();
-  }
-  const int Cout = dy.size(1);
-  const long Mtot = (long)N * OH * OW;
-  const int cpad = (int)((Cin + 63) / 64) * 64;
-  const int tiles_o = (Cout + 63) / 64;
-  // path (generic per-tap | halo-staged) and its split-M chunk count;
-  // the partials buffer below is sized for whichever path runs
-  TORCH_CHECK(algo >= -1 && algo <= 1, "conv_gemm_wrw: algo must be -1, 0, 1");
+  const ConvGeom g = cg_wrw_geom(dy, x, x2, KH, KW, sH, sW);
   int nchunk = 1;
-  const int path = flowhip_conv_gemm_wrw_plan(
-      Mtot, OH, OW, H, W, (int)sH, (int)sW, x2p != nullptr, C1, Cout, cpad,
-      (int)KH, (int)KW, (int)KH / 2, (int)KW / 2, (int)algo, (int)nchunk_req,
-      &nchunk);
-  TORCH_CHECK(path >= 0,
-              "conv_gemm_wrw: algo=1 (halo) forced on a shape outside its "
-              "envelope (stride 1, same padding, 3x3 / 1x5 / 5x1)");
-  // bias partials (nchunk, tiles_o*64) ride at the tail of the same
-  // buffer; dbias is written fully by the reduce kernel — no zero-fill
-  auto partials = torch::empty(
-      {(long)nchunk * KH * KW * tiles_o * 64 * cpad +
-       (want_bias ? (long)nchunk * tiles_o * 64 : 0)},
-      x.options().dtype(torch::kFloat32));
-  auto dw = torch::empty({(long)Cout, (long)Cin, KH, KW},
-                         x.options().dtype(torch::kFloat32));
+  const int path = cg_wrw_plan(g, algo, nchunk_req, &nchunk);
+  // every slot the reduce reads is written by the partials launch, and
+  // dw / dbias fully by the reduce: no zero-fill
+  const auto f32 = x.options().dtype(torch::kFloat32);
+  auto partials = torch::empty({g.buffer_numel(nchunk, want_bias)}, f32);
+  auto dw = torch::empty({(long)g.Cout, (long)g.Cin, KH, KW}, f32);
   torch::Tensor dbias;
-  if (want_bias)
-    dbias = torch::empty({(long)Cout}, x.options().dtype(torch::kFloat32));
+  if (want_bias) dbias = torch::empty({(long)g.Cout}, f32);
   const c10::cuda::CUDAGuard guard(x.device());
   hipStream_t stream = at::cuda::getCurrentCUDAStream().stream();
-  const bool launched = flowhip_conv_gemm_wrw_launch(dy.data_ptr(), x.data_ptr(), x2p,
-                               partials.data_ptr<float>(),
-                               dw.data_ptr<float>(),
-                               want_bias ? dbias.data_ptr<float>() : nullptr,
-                               cg_zero_page(), Mtot,
-                               OH, OW, H, W, (int)sH, (int)sW,
-                               ld_x, ld_x2, C1, Cin, Cout, cpad, (int)KH,
-                               (int)KW, (int)KH / 2, (int)KW / 2, nchunk,
-                               path, stream);
+  const bool launched = flowhip_conv_gemm_wrw_partials_launch(
+      dy.data_ptr(), x.data_ptr(), cg_ptr(x2), partials.data_ptr<float>(),
+      want_bias, cg_zero_page(), g, nchunk, path, false, stream);
   TORCH_CHECK(launched,
               "conv_gemm_wrw: the halo kernel refused a planned shape");
+  flowhip_conv_gemm_wrw_finish_launch(
+      partials.data_ptr<float>(), dw.data_ptr<float>(),
+      want_bias ? dbias.data_ptr<float>() : nullptr, g, nchunk, false,
+      stream);
   return {dw, dbias};
 }
-
-// The same weight gradient as three steps, for callers that sum the
-// gradients of several calls (same weights, same shapes) in one partials
-// buffer and reduce once: plan -> partials (accumulate) x K -> finish.
-namespace {
-struct WrwGeom {
-  int N, C1, H, W, OH, OW, Cin, Cout, cpad, tiles_o, ld_x, ld_x2;
-  long Mtot;
-  const void* x2p;
-};
-
-WrwGeom wrw_geom(const torch::Tensor& dy, const torch::Tensor& x,
-                 const c10::optional<torch::Tensor>& x2) {
-  WrwGeom g;
-  g.ld_x2 = 0;
-  cg_check_x(x, g.ld_x);
-  TORCH_CHECK(dy.is_cuda() && dy.dim() == 4 &&
-              dy.scalar_type() == torch::kBFloat16 && dy.stride(1) == 1 &&
-              dy.stride(3) == dy.size(1),
-              "conv_gemm_wrw: dy must be channels-last contiguous");
-  g.N = x.size(0); g.C1 = x.size(1); g.H = x.size(2); g.W = x.size(3);
-  g.OH = dy.size(2); g.OW = dy.size(3);
-  TORCH_CHECK(dy.size(0) == g.N);
-  g.Cin = g.C1;
-  g.x2p = nullptr;
-  if (x2.has_value()) {
-    cg_check_x(x2.value(), g.ld_x2);
-    TORCH_CHECK(x2->size(0) == g.N && x2->size(2) == g.H &&
-                x2->size(3) == g.W);
-    g.Cin = g.C1 + (int)x2->size(1);
-    g.x2p = x2->data_ptr();
-  }
-  g.Cout = dy.size(1);
-  g.Mtot = (long)g.N * g.OH * g.OW;
-  g.cpad = (g.Cin + 63) / 64 * 64;
-  g.tiles_o = (g.Cout + 63) / 64;
-  return g;
-}
-
-long wrw_buffer_numel(const WrwGeom& g, int64_t KH, int64_t KW, int nchunk,
-                      bool want_bias) {
-  return (long)nchunk * KH * KW * g.tiles_o * 64 * g.cpad +
-         (want_bias ? (long)nchunk * g.tiles_o * 64 : 0);
-}
-}  // namespace
 
 // -> (path, nchunk, buffer elements, accumulate). The buffer size includes
 // the bias partials when want_bias. accumulate: 1 where calls that share a
@@ -1343,17 +1268,10 @@ std::vector<int64_t> conv_gemm_wrw_plan(torch::Tensor dy, torch::Tensor x,
                                         int64_t KH, int64_t KW, int64_t sH,
                                         int64_t sW, bool want_bias,
                                         int64_t algo, int64_t nchunk_req) {
-  const WrwGeom g = wrw_geom(dy, x, x2);
-  TORCH_CHECK(algo >= -1 && algo <= 1, "conv_gemm_wrw: algo must be -1, 0, 1");
+  const ConvGeom g = cg_wrw_geom(dy, x, x2, KH, KW, sH, sW);
   int nchunk = 1;
-  const int path = flowhip_conv_gemm_wrw_plan(
-      g.Mtot, g.OH, g.OW, g.H, g.W, (int)sH, (int)sW, g.x2p != nullptr, g.C1,
-      g.Cout, g.cpad, (int)KH, (int)KW, (int)KH / 2, (int)KW / 2, (int)algo,
-      (int)nchunk_req, &nchunk);
-  TORCH_CHECK(path >= 0,
-              "conv_gemm_wrw: algo=1 (halo) forced on a shape outside its "
-              "envelope (stride 1, same padding, 3x3 / 1x5 / 5x1)");
-  return {path, nchunk, wrw_buffer_numel(g, KH, KW, nchunk, want_bias),
+  const int path = cg_wrw_plan(g, algo, nchunk_req, &nchunk);
+  return {path, nchunk, g.buffer_numel(nchunk, want_bias),
           flowhip_conv_gemm_wrw_accumulate_wins(path) ? 1 : 0};
 }
 
@@ -1365,34 +1283,26 @@ void conv_gemm_wrw_partials(torch::Tensor dy, torch::Tensor x,
                             torch::Tensor partials, int64_t KH, int64_t KW,
                             int64_t sH, int64_t sW, bool want_bias,
                             bool accumulate, int64_t algo, int64_t nchunk) {
-  const WrwGeom g = wrw_geom(dy, x, x2);
+  const ConvGeom g = cg_wrw_geom(dy, x, x2, KH, KW, sH, sW);
   TORCH_CHECK(algo == 0 || algo == 1,
               "conv_gemm_wrw_partials: algo must be a planned path (0 | 1)");
   int planned = 0;
-  const int path = flowhip_conv_gemm_wrw_plan(
-      g.Mtot, g.OH, g.OW, g.H, g.W, (int)sH, (int)sW, g.x2p != nullptr, g.C1,
-      g.Cout, g.cpad, (int)KH, (int)KW, (int)KH / 2, (int)KW / 2, (int)algo,
-      (int)nchunk, &planned);
+  const int path =
+      flowhip_conv_gemm_wrw_plan(g, (int)algo, (int)nchunk, &planned);
   TORCH_CHECK(path == algo && planned == nchunk && nchunk >= 1,
               "conv_gemm_wrw_partials: (algo, nchunk) is not a plan for "
               "these shapes");
   TORCH_CHECK(partials.is_cuda() && partials.is_contiguous() &&
               partials.scalar_type() == torch::kFloat32 &&
               partials.device() == x.device() &&
-              partials.numel() ==
-                  wrw_buffer_numel(g, KH, KW, (int)nchunk, want_bias),
+              partials.numel() == g.buffer_numel((int)nchunk, want_bias),
               "conv_gemm_wrw_partials: buffer does not match the plan");
-  float* pp = partials.data_ptr<float>();
-  float* biasp =
-      want_bias ? pp + wrw_buffer_numel(g, KH, KW, (int)nchunk, false)
-                : nullptr;
   const c10::cuda::CUDAGuard guard(x.device());
   hipStream_t stream = at::cuda::getCurrentCUDAStream().stream();
   const bool launched = flowhip_conv_gemm_wrw_partials_launch(
-      dy.data_ptr(), x.data_ptr(), g.x2p, pp, biasp, cg_zero_page(), g.Mtot,
-      g.OH, g.OW, g.H, g.W, (int)sH, (int)sW, g.ld_x, g.ld_x2, g.C1, g.Cin,
-      g.Cout, g.cpad, (int)KH, (int)KW, (int)KH / 2, (int)KW / 2, (int)nchunk,
-      (int)algo, accumulate, stream);
+      dy.data_ptr(), x.data_ptr(), cg_ptr(x2), partials.data_ptr<float>(),
+      want_bias, cg_zero_page(), g, (int)nchunk, (int)algo, accumulate,
+      stream);
   TORCH_CHECK(launched,
               "conv_gemm_wrw: the halo kernel refused a planned shape");
 }
@@ -1406,12 +1316,12 @@ std::vector<torch::Tensor> conv_gemm_wrw_finish(
     c10::optional<torch::Tensor> dw_into,
     c10::optional<torch::Tensor> dbias_into) {
   TORCH_CHECK(Cout >= 1 && Cin >= 1 && KH >= 1 && KW >= 1 && nchunk >= 1);
-  const long cpad = (Cin + 63) / 64 * 64;
-  const long orows = (Cout + 63) / 64 * 64;
-  const long wnumel = nchunk * KH * KW * orows * cpad;
+  ConvGeom g{};  // the reduce needs the buffer layout only
+  g.Cout = (int)Cout; g.Cin = (int)Cin; g.cpad = cg_cpad(g.Cin);
+  g.KH = (int)KH; g.KW = (int)KW;
   TORCH_CHECK(partials.is_cuda() && partials.is_contiguous() &&
               partials.scalar_type() == torch::kFloat32 &&
-              partials.numel() == wnumel + (want_bias ? nchunk * orows : 0),
+              partials.numel() == g.buffer_numel((int)nchunk, want_bias),
               "conv_gemm_wrw_finish: buffer does not match the shapes");
   const bool accumulate = dw_into.has_value();
   TORCH_CHECK(dbias_into.has_value() == (accumulate && want_bias),
@@ -1435,13 +1345,12 @@ std::vector<torch::Tensor> conv_gemm_wrw_finish(
     dw = torch::empty({Cout, Cin, KH, KW}, partials.options());
     if (want_bias) dbias = torch::empty({Cout}, partials.options());
   }
-  const float* pp = partials.data_ptr<float>();
   const c10::cuda::CUDAGuard guard(partials.device());
   hipStream_t stream = at::cuda::getCurrentCUDAStream().stream();
   flowhip_conv_gemm_wrw_finish_launch(
-      pp, want_bias ? pp + wnumel : nullptr, dw.data_ptr<float>(),
-      want_bias ? dbias.data_ptr<float>() : nullptr, (int)Cin, (int)Cout,
-      (int)cpad, (int)KH, (int)KW, (int)nchunk, accumulate, stream);
+      partials.data_ptr<float>(), dw.data_ptr<float>(),
+      want_bias ? dbias.data_ptr<float>() : nullptr, g, (int)nchunk,
+      accumulate, stream);
   return {dw, dbias};
 }
 

@@ -35,7 +35,10 @@
 //              tap geometry) and the halo-staged kernel of
 //              conv_wrw_halo.hip (stride-1 same-padding 3x3 / 1x5 / 5x1),
 //              which stages dy and one x halo tile once for all taps.
-//              flowhip_conv_gemm_wrw_plan picks the path.
+//              flowhip_conv_gemm_wrw_plan (conv_gemm.h) picks the path.
+//
+// Host side: the launchers at the end of this file take a ConvGeom
+// (conv_gemm.h), which also holds the plan and every launcher's prototype.
 //
 // Weight packing (host side, cached per weight version):
 //   wpk[kyx][o][c_pad]  (c_pad = roundup(Cin, 64), zero-filled)
@@ -43,7 +46,7 @@
 // the per-lane glds source address.
 
 #include "common.h"
-#include "conv_wrw_halo_maps.h"
+#include "conv_gemm.h"
 
 #define CG_BM 64
 #define CG_BN 64
@@ -635,256 +638,109 @@ __global__ __launch_bounds__(CG_THREADS) void conv_gemm_wrw_reduce_kernel(
 template <int BM>
 static void cg_fwd_dispatch(const __bf16* x, const __bf16* x2,
                             const __bf16* wpk, const float* bias, __bf16* out,
-                            __bf16* out2, const __bf16* zpage, long Mtot,
-                            int HH, int WW, int srcH, int srcW, int sH,
-                            int sW, int ld_x, int ld_x2, int C1, int Cin,
-                            int Cout, int cpad, int KH, int KW, int offH,
-                            int offW, int osplit, int act, int smode,
+                            __bf16* out2, const __bf16* zpage,
+                            const ConvGeom& g, int osplit, int act, int smode,
                             hipStream_t stream) {
-  const int tiles_m = (int)((Mtot + BM - 1) / BM);
-  const int tiles_n = fh_cdiv(Cout, CG_BN);
+  // tap offsets: direct conv (smode 0/1) reads sy = oy*sH + ky - padH;
+  // strided-transposed (smode 2) taps t = iy + ky + (padH - KH + 1)
+  const int offH = smode == 2 ? g.padH - g.KH + 1 : -g.padH;
+  const int offW = smode == 2 ? g.padW - g.KW + 1 : -g.padW;
+  const int tiles_m = (int)((g.Mtot + BM - 1) / BM);
+  const int tiles_n = fh_cdiv(g.Cout, CG_BN);
   dim3 grid(tiles_m * tiles_n), block(BM == 64 ? 256 : 512);
 #define CG_LAUNCH(A, S)                                                      \
   hipLaunchKernelGGL((conv_gemm_fwd_kernel<A, BM, S>), grid, block, 0,       \
-                     stream, x, x2, wpk, bias, out, out2, zpage, Mtot, HH,   \
-                     WW, srcH, srcW, sH, sW, ld_x, ld_x2, C1, Cin, Cout,     \
-                     cpad, KH, KW, offH, offW, osplit, tiles_m)
+                     stream, x, x2, wpk, bias, out, out2, zpage, g.Mtot,     \
+                     g.HH, g.WW, g.srcH, g.srcW, g.sH, g.sW, g.ld_x,         \
+                     g.ld_x2, g.C1, g.Cin, g.Cout, g.cpad, g.KH, g.KW, offH, \
+                     offW, osplit, tiles_m)
   if (smode == 0) { if (act == 1) CG_LAUNCH(1, 0); else CG_LAUNCH(0, 0); }
   else if (smode == 1) { if (act == 1) CG_LAUNCH(1, 1); else CG_LAUNCH(0, 1); }
   else { if (act == 1) CG_LAUNCH(1, 2); else CG_LAUNCH(0, 2); }
 #undef CG_LAUNCH
 }
 
-bool flowhip_conv_halo_fwd_launch(const void* x, const void* x2,
-                                  const void* wpk, const float* bias,
-                                  void* out, const void* zpage, int N,
-                                  int H, int W, int ld_x, int ld_x2, int C1,
-                                  int Cin, int Cout, int cpad, int ldo,
-                                  int KH, int KW, int act,
-                                  hipStream_t stream);
-
 void flowhip_conv_gemm_fwd_launch(const void* x, const void* x2,
                                   const void* wpk, const float* bias,
                                   void* out, void* out2, const void* zpage,
-                                  long Mtot, int HH, int WW, int srcH,
-                                  int srcW, int sH, int sW, int ld_x,
-                                  int ld_x2, int C1, int Cin, int Cout,
-                                  int cpad, int KH, int KW, int padH,
-                                  int padW, int osplit, int act, int smode,
-                                  hipStream_t stream) {
+                                  const ConvGeom& g, int osplit, int act,
+                                  int smode, hipStream_t stream) {
   // stride-1 3x3 / 1x5 / 5x1 (the dominant shapes incl. their
   // backward-data): the halo-staged kernel stages the input once for all
   // KH*KW taps
-  if (smode == 0 && out2 == nullptr && padH == KH / 2 && padW == KW / 2 &&
-      ((KH == 3 && KW == 3) || (KH == 1 && KW == 5) ||
-       (KH == 5 && KW == 1))) {
-    const int N = (int)(Mtot / ((long)HH * WW));
-    if (flowhip_conv_halo_fwd_launch(x, x2, wpk, bias, out, zpage, N, HH,
-                                     WW, ld_x, ld_x2, C1, Cin, Cout, cpad,
-                                     Cout, KH, KW, act, stream))
-      return;
-  }
-  // tap offsets: direct conv (smode 0/1) reads sy = oy*sH + ky - padH;
-  // strided-transposed (smode 2) taps t = iy + ky + (padH - KH + 1)
-  const int offH = smode == 2 ? padH - KH + 1 : -padH;
-  const int offW = smode == 2 ? padW - KW + 1 : -padW;
+  if (smode == 0 && out2 == nullptr &&
+      flowhip_conv_halo_fwd_launch(x, x2, wpk, bias, out, zpage, g, act,
+                                   stream))
+    return;
   // Tile choice: BM=128 once the grid still fills the 256-CU chip; the
   // encoder shapes (M >= 64k) take it, the update block (M ~ 21k, 168
   // M-tiles at BM=128) keeps the fill-first 64x64 tile.
-  const long t128 = ((Mtot + 127) / 128) * fh_cdiv(Cout, CG_BN);
+  const long t128 = ((g.Mtot + 127) / 128) * fh_cdiv(g.Cout, CG_BN);
   if (t128 >= 320)
     cg_fwd_dispatch<128>((const __bf16*)x, (const __bf16*)x2,
                          (const __bf16*)wpk, bias, (__bf16*)out,
-                         (__bf16*)out2, (const __bf16*)zpage, Mtot, HH, WW,
-                         srcH, srcW, sH, sW, ld_x, ld_x2, C1, Cin, Cout,
-                         cpad, KH, KW, offH, offW, osplit, act, smode,
-                         stream);
+                         (__bf16*)out2, (const __bf16*)zpage, g, osplit, act,
+                         smode, stream);
   else
     cg_fwd_dispatch<64>((const __bf16*)x, (const __bf16*)x2,
                         (const __bf16*)wpk, bias, (__bf16*)out, (__bf16*)out2,
-                        (const __bf16*)zpage, Mtot, HH, WW, srcH, srcW, sH,
-                        sW, ld_x, ld_x2, C1, Cin, Cout, cpad, KH, KW, offH,
-                        offW, osplit, act, smode, stream);
+                        (const __bf16*)zpage, g, osplit, act, smode, stream);
 }
 
-bool flowhip_conv_wrw_halo_launch(const void* dy, const void* x,
-                                  const void* x2, float* partials,
-                                  float* biasp, const void* zpage, int N,
-                                  int H, int W, int ld_x, int ld_x2, int C1,
-                                  int Cin, int Cout, int cpad, int KH, int KW,
-                                  int nchunk, bool accumulate,
-                                  hipStream_t stream);
-
-// Chooses the weight-gradient path and its split-M chunk count; the caller
-// sizes the partials buffer (nchunk * KYX * tiles_o*64 * cpad weight
-// partials + nchunk * tiles_o*64 bias partials) from the result.
-//   algo: -1 auto, 0 generic per-tap kernel, 1 halo-staged kernel
-//         (conv_wrw_halo.hip). Returns the path taken (0 | 1), or -1 when
-//         algo == 1 was forced on a shape outside the halo envelope.
-//   nchunk_req: 0 = the path's own choice, else forced (clamped).
-int flowhip_conv_gemm_wrw_plan(long Mtot, int HH, int WW, int srcH, int srcW,
-                               int sH, int sW, bool has_x2, int C1, int Cout,
-                               int cpad, int KH, int KW, int padH, int padW,
-                               int algo, int nchunk_req, int* nchunk_out) {
-  const int tiles_o = fh_cdiv(Cout, 64);
-  const int tiles_c = fh_cdiv(cpad, 64);
-  // halo envelope: stride 1, same padding, the three tap geometries the
-  // forward halo kernel covers
-  const bool eligible =
-      sH == 1 && sW == 1 && srcH == HH && srcW == WW && padH == KH / 2 &&
-      padW == KW / 2 &&
-      ((KH == 3 && KW == 3) || (KH == 1 && KW == 5) ||
-       (KH == 5 && KW == 1)) &&
-      cpad % 64 == 0 && Cout % 8 == 0 && (!has_x2 || C1 % 64 == 0) &&
-      Mtot <= 0x7fffffffL;
-  if (algo == 1 && !eligible) return -1;
-  const long ptiles = eligible ? (Mtot / ((long)HH * WW)) *
-                                     fh_cdiv(HH, WH_TH) * fh_cdiv(WW, WH_TW)
-                               : 0;
-  // auto follows tools/bench_wrw.py (profiles/README.md round 3): the halo
-  // kernel wins where one staged tile pair feeds enough output tiles or a
-  // long pixel walk — 8+ output tiles (update block: 256->192, 256->126,
-  // 128->256 3x3 and the 384-channel 1x5 / 5x1 GRU convs, 6-22% faster),
-  // or 4+ output tiles over 672+ pixel tiles (96-channel encoder stage,
-  // 20-39%). It measured SLOWER, and stays on the generic kernel, for
-  // 128->64 and 256->2 at 56x128 (2-4 output tiles: too few workgroups
-  // for a kernel that owns its CU) and for the 64- and 128-channel
-  // encoder stages. The rule is fitted to those measured classes only: the
-  // 672 threshold is the batch-3 96-channel encoder shape, the smallest
-  // 4-tile class that won; nothing between the measured points is known.
-  const int tiles = tiles_o * tiles_c;
-  const bool wins = tiles >= 8 || (tiles >= 4 && ptiles >= 672);
-  const bool halo = eligible && (algo == 1 || (algo == -1 && wins));
-  if (halo) {
-    long n = nchunk_req > 0 ? nchunk_req : wh_nchunk(ptiles, tiles_o * tiles_c);
-    if (n > ptiles) n = ptiles;
-    if (n > 4096) n = 4096;
-    *nchunk_out = (int)n;
-    return 1;
-  }
-  // generic: split M only as much as needed to fill the chip (~2 blocks
-  // per CU); more chunks = more fp32 partial traffic + a longer reduce
-  const int base_tiles = tiles_o * tiles_c * KH * KW;
-  int nchunk = nchunk_req > 0 ? nchunk_req
-                              : (512 + base_tiles - 1) / base_tiles;
-  if (nchunk < 1) nchunk = 1;
-  if (nchunk > 64) nchunk = 64;  // encoder shapes: few tiles, huge M
-  // never more chunks than 64-row m-tiles
-  const long mtiles = (Mtot + 63) / 64;
-  if (nchunk > mtiles) nchunk = (int)mtiles;
-  *nchunk_out = nchunk;
-  return 0;
-}
-
-// Whether calls that share a weight should sum their partials in one
-// buffer (partials launch with accumulate, one finish at the end) or run
-// one-shot partials and add each call's reduce to a running dW (finish
-// with accumulate). Measured per backward pass of 12 calls at 3x56x128 on
-// MI355X (tools/bench_wrw.py --accumulate, median of 5 alternating rounds,
-// min-max within 1%; profiles/README.md round 5). Columns: 12 one-shot
-// calls + 11 fp32 adds of dW and dbias | 12 accumulating calls + 1 finish
-// | 12 one-shot partials each with a finish into the running dW; in us.
-//   generic path: accumulating partials wins on every shape
-//     128->64 3x3    428 | 215 | 385      256->2 3x3    453 | 321 | 414
-//     324->256 1x1   491 | 320 | 456      8->128 7x7    702 | 614 | 666
-//   halo path: accumulating partials loses on every shape, the finish
-//   into the running dW wins
-//     256->192 3x3   705 |  965 | 665     384->256 1x5  818 |  939 | 774
-//     256->126 3x3   593 |  817 | 554     384->256 5x1  911 | 1037 | 867
-//     128->256 3x3   595 |  741 | 554     384->128 1x5  567 |  643 | 528
-//                                         384->128 5x1  613 |  700 | 575
-// The halo kernel owns its CU at one wave per SIMD, so nothing hides the
-// latency of its epilogue's 16 * KYX loads per thread, and in the training
-// step its 15-27 MB buffers leave the cache between two iterations: +41 us
-// per launch in the kernel trace, against 13 us of reduce and 9 us of adds
-// saved. The rule follows the two measured classes.
-bool flowhip_conv_gemm_wrw_accumulate_wins(int path) { return path == 0; }
-
-// The weight gradient runs in two steps that share one partials buffer.
-// algo / nchunk: as returned by flowhip_conv_gemm_wrw_plan.
+// The weight gradient runs in two steps that share one partials buffer;
+// the plan that picks the path and its chunk count is in conv_gemm.h.
 //
 // Step 1, partials: one launch of the planned partials kernel. accumulate
 // == false overwrites every slot of the buffer the reduce will read (no
 // zero-fill needed); accumulate == true adds this call's sums to what the
 // buffer holds, so K calls with the same weights (the refinement loop)
 // leave the sum of their K gradients in the slots and need ONE reduce.
-// biasp == nullptr skips the bias gradient. Returns false (nothing
+// want_bias == false skips the bias gradient. Returns false (nothing
 // launched) if the halo kernel refuses a planned shape.
-bool flowhip_conv_gemm_wrw_partials_launch(
-    const void* dy, const void* x, const void* x2, float* partials,
-    float* biasp, const void* zpage, long Mtot, int HH, int WW, int srcH,
-    int srcW, int sH, int sW, int ld_x, int ld_x2, int C1, int Cin, int Cout,
-    int cpad, int KH, int KW, int padH, int padW, int nchunk, int algo,
-    bool accumulate, hipStream_t stream) {
-  const int tiles_o = fh_cdiv(Cout, 64);
-  const int tiles_c = fh_cdiv(cpad, 64);
-  if (algo == 1) {
-    // halo-staged kernel: one staging of dy and of an x halo tile serves
-    // all KH*KW taps; same partials layout, same reduce
-    const int N = (int)(Mtot / ((long)HH * WW));
-    // false: the plan admitted a shape the kernel refuses, a bug the
-    // caller reports, not a fall-back case
-    return flowhip_conv_wrw_halo_launch(dy, x, x2, partials, biasp, zpage, N,
-                                        HH, WW, ld_x, ld_x2, C1, Cin, Cout,
-                                        cpad, KH, KW, nchunk, accumulate,
-                                        stream);
-  }
+bool flowhip_conv_gemm_wrw_partials_launch(const void* dy, const void* x,
+                                           const void* x2, float* partials,
+                                           bool want_bias, const void* zpage,
+                                           const ConvGeom& g, int nchunk,
+                                           int algo, bool accumulate,
+                                           hipStream_t stream) {
+  float* biasp = want_bias ? g.biasp(partials, nchunk) : nullptr;
+  // halo-staged kernel: one staging of dy and of an x halo tile serves
+  // all KH*KW taps; same partials layout, same reduce.
+  // false: the plan admitted a shape the kernel refuses, a bug the
+  // caller reports, not a fall-back case
+  if (algo == 1)
+    return flowhip_conv_wrw_halo_launch(dy, x, x2, partials, biasp, zpage, g,
+                                        nchunk, accumulate, stream);
   // (a KW=3 tap-sharing wrw variant that shared only dy and kept one x
   // image per tap was measured SLOWER despite 3x less operand re-read:
   // the 4-image LDS set halves occupancy — within-box A/B 41.0 vs 42.65
   // pairs/s. The halo kernel above keeps ONE x image.)
-  dim3 grid(tiles_o * tiles_c, KH * KW, nchunk), block(CG_THREADS);
+  dim3 grid(g.tiles_o() * g.tiles_c(), g.KH * g.KW, nchunk),
+      block(CG_THREADS);
   hipLaunchKernelGGL(conv_gemm_wrw_kernel, grid, block, 0, stream,
                      (const __bf16*)dy, (const __bf16*)x, (const __bf16*)x2,
-                     partials, biasp, (const __bf16*)zpage, Mtot, HH, WW,
-                     srcH, srcW, sH, sW, ld_x, ld_x2, C1, Cin, Cout, cpad, KH,
-                     KW, padH, padW, tiles_o, tiles_c, nchunk,
-                     accumulate ? 1 : 0);
+                     partials, biasp, (const __bf16*)zpage, g.Mtot, g.HH,
+                     g.WW, g.srcH, g.srcW, g.sH, g.sW, g.ld_x, g.ld_x2, g.C1,
+                     g.Cin, g.Cout, g.cpad, g.KH, g.KW, g.padH, g.padW,
+                     g.tiles_o(), g.tiles_c(), nchunk, accumulate ? 1 : 0);
   return true;
 }
 
 // Step 2, finish: sum the chunks (ascending) into dW (Cout, Cin, KH, KW)
-// and, with biasp / dbias given, into dbias (Cout). accumulate adds the
-// sums to what dW / dbias hold instead of overwriting them.
-void flowhip_conv_gemm_wrw_finish_launch(const float* partials,
-                                         const float* biasp, float* dw,
-                                         float* dbias, int Cin, int Cout,
-                                         int cpad, int KH, int KW, int nchunk,
-                                         bool accumulate,
+// and, with dbias given, the bias partials into dbias (Cout). accumulate
+// adds the sums to what dW / dbias hold instead of overwriting them.
+void flowhip_conv_gemm_wrw_finish_launch(const float* partials, float* dw,
+                                         float* dbias, const ConvGeom& g,
+                                         int nchunk, bool accumulate,
                                          hipStream_t stream) {
-  const int tiles_o = fh_cdiv(Cout, 64);
-  const long total = (long)Cout * Cin * KH * KW;
+  const long total = (long)g.Cout * g.Cin * g.KH * g.KW;
   long rblocks = (total + CG_THREADS - 1) / CG_THREADS;
   if (rblocks > 4096) rblocks = 4096;
   hipLaunchKernelGGL(conv_gemm_wrw_reduce_kernel, dim3((int)rblocks),
-                     dim3(CG_THREADS), 0, stream, partials, dw, biasp, dbias,
-                     nchunk, KH * KW, tiles_o * 64, cpad, Cout, Cin,
-                     accumulate ? 1 : 0);
-}
-
-// One-shot weight gradient: partials (overwrite) + finish. The bias
-// partials live past the weight partials (caller sized the buffer).
-bool flowhip_conv_gemm_wrw_launch(const void* dy, const void* x,
-                                  const void* x2, float* partials, float* dw,
-                                  float* dbias, const void* zpage, long Mtot,
-                                  int HH,
-                                  int WW, int srcH, int srcW, int sH, int sW,
-                                  int ld_x, int ld_x2, int C1, int Cin,
-                                  int Cout, int cpad, int KH, int KW,
-                                  int padH, int padW, int nchunk, int algo,
-                                  hipStream_t stream) {
-  const int tiles_o = fh_cdiv(Cout, 64);
-  float* biasp = dbias
-      ? partials + (long)nchunk * KH * KW * tiles_o * 64 * cpad
-      : nullptr;
-  if (!flowhip_conv_gemm_wrw_partials_launch(
-          dy, x, x2, partials, biasp, zpage, Mtot, HH, WW, srcH, srcW, sH, sW,
-          ld_x, ld_x2, C1, Cin, Cout, cpad, KH, KW, padH, padW, nchunk, algo,
-          false, stream))
-    return false;
-  flowhip_conv_gemm_wrw_finish_launch(partials, biasp, dw, dbias, Cin, Cout,
-                                      cpad, KH, KW, nchunk, false, stream);
-  return true;
+                     dim3(CG_THREADS), 0, stream, partials, dw,
+                     dbias ? g.biasp(partials, nchunk) : nullptr, dbias,
+                     nchunk, g.KH * g.KW, g.tiles_o() * 64, g.cpad, g.Cout,
+                     g.Cin, accumulate ? 1 : 0);
 }
 
 // ---------------------------------------------------------------------------

@@ -25,6 +25,7 @@
 // B row and masks the store.
 
 #include "common.h"
+#include "conv_gemm.h"
 
 #define CH_TW 32
 #define CH_THREADS 256
@@ -192,27 +193,27 @@ __global__ __launch_bounds__(CH_THREADS, 4) void conv_halo3_fwd_kernel(
 
 bool flowhip_conv_halo_fwd_launch(const void* x, const void* x2,
                                   const void* wpk, const float* bias,
-                                  void* out, const void* zpage, int N,
-                                  int H, int W, int ld_x, int ld_x2, int C1,
-                                  int Cin, int Cout, int cpad, int ldo,
-                                  int KH, int KW, int act,
+                                  void* out, const void* zpage,
+                                  const ConvGeom& g, int act,
                                   hipStream_t stream) {
-  if (cpad % 64 != 0) return false;
-  const int nco = fh_cdiv(Cout, 64);
+  if (!g.halo_envelope()) return false;
+  const int N = g.N(), nco = g.tiles_o();
   // single-slab inputs (Cin <= 64): taller single-buffered tile
-  const int THT = (cpad == 64) ? 8 : 4;
-  const int ntx = fh_cdiv(W, CH_TW), nty = fh_cdiv(H, THT);
+  const int THT = (g.cpad == 64) ? 8 : 4;
+  const int ntx = fh_cdiv(g.WW, CH_TW), nty = fh_cdiv(g.HH, THT);
   const long blocks = (long)ntx * nty * nco * N;
   if (blocks < 320) return false;  // fill-first: generic kernel handles it
   dim3 grid((unsigned)blocks), block(CH_THREADS);
+  // output rows are dense: ldo = Cout
 #define CH_LAUNCH(A, T, D, KHH, KWW)                                         \
   hipLaunchKernelGGL((conv_halo3_fwd_kernel<A, T, D, KHH, KWW>), grid,       \
                      block, 0, stream, (const __bf16*)x,                     \
                      (const __bf16*)x2, (const __bf16*)wpk, bias,            \
-                     (__bf16*)out, (const __bf16*)zpage, N, H, W, ld_x,      \
-                     ld_x2, C1, Cin, Cout, cpad, ldo, ntx, nty, nco)
+                     (__bf16*)out, (const __bf16*)zpage, N, g.HH, g.WW,      \
+                     g.ld_x, g.ld_x2, g.C1, g.Cin, g.Cout, g.cpad, g.Cout,   \
+                     ntx, nty, nco)
 #define CH_GEOM(KHH, KWW)                                                    \
-  if (KH == KHH && KW == KWW) {                                              \
+  if (g.KH == KHH && g.KW == KWW) {                                          \
     if (THT == 8) {                                                          \
       if (act == 1) CH_LAUNCH(1, 8, false, KHH, KWW);                        \
       else CH_LAUNCH(0, 8, false, KHH, KWW);                                 \

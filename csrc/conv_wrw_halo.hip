@@ -36,7 +36,7 @@
 // accumulate the bias gradient from the dy fragments they already hold.
 
 #include "common.h"
-#include "conv_wrw_halo_maps.h"
+#include "conv_gemm.h"
 
 typedef __attribute__((ext_vector_type(4))) short wh_s16x4;
 typedef __attribute__((ext_vector_type(8))) short wh_s16x8;
@@ -274,29 +274,24 @@ __global__ __launch_bounds__(WH_THREADS) void conv_wrw_halo_kernel(
 // Returns false (nothing launched) outside the envelope.
 bool flowhip_conv_wrw_halo_launch(const void* dy, const void* x,
                                   const void* x2, float* partials,
-                                  float* biasp, const void* zpage, int N,
-                                  int H, int W, int ld_x, int ld_x2, int C1,
-                                  int Cin, int Cout, int cpad, int KH, int KW,
-                                  int nchunk, bool accumulate,
-                                  hipStream_t stream) {
-  if (cpad % 64 != 0 || Cout % 8 != 0) return false;
-  if (x2 != nullptr && C1 % 64 != 0) return false;
-  const int tiles_o = fh_cdiv(Cout, 64), tiles_c = cpad / 64;
-  const int ntx = fh_cdiv(W, WH_TW), nty = fh_cdiv(H, WH_TH);
+                                  float* biasp, const void* zpage,
+                                  const ConvGeom& g, int nchunk,
+                                  bool accumulate, hipStream_t stream) {
+  if (!g.wrw_halo_envelope()) return false;
+  const int N = g.N(), tiles_o = g.tiles_o();
+  const int ntx = fh_cdiv(g.WW, WH_TW), nty = fh_cdiv(g.HH, WH_TH);
   const long ptiles = (long)N * nty * ntx;
-  // the staging maps index pixels in 32 bits
-  if (nchunk < 1 || nchunk > ptiles || nchunk > 65535 ||
-      (long)N * H * W > 0x7fffffffL)
-    return false;
-  dim3 grid(tiles_o * tiles_c, nchunk), block(WH_THREADS);
+  // the chunk index is blockIdx.y
+  if (nchunk < 1 || nchunk > ptiles || nchunk > 65535) return false;
+  dim3 grid(tiles_o * g.tiles_c(), nchunk), block(WH_THREADS);
 #define WH_LAUNCH(KHH, KWW)                                                  \
-  if (KH == KHH && KW == KWW) {                                              \
+  if (g.KH == KHH && g.KW == KWW) {                                          \
     hipLaunchKernelGGL((conv_wrw_halo_kernel<KHH, KWW>), grid, block, 0,     \
                        stream, (const __bf16*)dy, (const __bf16*)x,          \
                        (const __bf16*)x2, partials, biasp,                   \
-                       (const __bf16*)zpage, N, H, W, ld_x, ld_x2, C1, Cin,  \
-                       Cout, cpad, tiles_o, ntx, nty, nchunk,                \
-                       accumulate ? 1 : 0);                                  \
+                       (const __bf16*)zpage, N, g.HH, g.WW, g.ld_x, g.ld_x2, \
+                       g.C1, g.Cin, g.Cout, g.cpad, tiles_o, ntx, nty,       \
+                       nchunk, accumulate ? 1 : 0);                          \
     return true;                                                             \
   }
   WH_LAUNCH(3, 3) WH_LAUNCH(1, 5) WH_LAUNCH(5, 1)

@@ -15,8 +15,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ..ops.functional_conv import (fused_conv2d, fused_conv2d_cat2,
-                                   fused_gru_zr_conv)
+from ..ops.functional_conv import (_weight_key, fused_conv2d,
+                                   fused_conv2d_cat2, fused_gru_zr_conv)
 
 
 class FusedConv2d(nn.Conv2d):
@@ -53,17 +53,16 @@ class ConvGRU(nn.Module):
         self.convz = FusedConv2d(hidden_dim + input_dim, hidden_dim, 3, padding=1)
         self.convr = FusedConv2d(hidden_dim + input_dim, hidden_dim, 3, padding=1)
         self.convq = FusedConv2d(hidden_dim + input_dim, hidden_dim, 3, padding=1)
+        self._zr_cache = {}
 
     def forward(self, h, x):
         hx = torch.cat([h, x], dim=1)
-        if not hasattr(self, "_zr_cache"):
-            self._zr_cache = {}
+        # the weight passed is a fresh cat: key the packing on its parts
         zr = fused_conv2d(
             hx, torch.cat([self.convz.weight, self.convr.weight]),
             torch.cat([self.convz.bias, self.convr.bias]), 1, 1, 1, 1,
             self._zr_cache,
-            key=(self.convz.weight.data_ptr(), self.convz.weight._version,
-                 self.convr.weight.data_ptr(), self.convr.weight._version))
+            key=_weight_key(self.convz.weight, self.convr.weight))
         if h.is_cuda:
             from ..ops.functional_gru import GruGate1Fn, GruGate2Fn
             z, rh = GruGate1Fn.apply(zr, h)
@@ -86,6 +85,8 @@ class SepConvGRU(nn.Module):
         self.convz2 = FusedConv2d(hidden_dim + input_dim, hidden_dim, (5, 1), padding=(2, 0))
         self.convr2 = FusedConv2d(hidden_dim + input_dim, hidden_dim, (5, 1), padding=(2, 0))
         self.convq2 = FusedConv2d(hidden_dim + input_dim, hidden_dim, (5, 1), padding=(2, 0))
+        self._zr1_cache, self._zr2_cache = {}, {}
+        self._q1_cache, self._q2_cache = {}, {}
 
     def _pass(self, h, x, convz, convr, convq, padding, zr_cache, q_cache):
         # packed z+r conv over the virtually-concatenated input: weights,
@@ -98,17 +99,13 @@ class SepConvGRU(nn.Module):
             from ..ops.functional_gru import GruGate1Fn, GruGate2Fn
             z, rh = GruGate1Fn.apply(zr, h)
             qp = fused_conv2d_cat2(rh, x, convq.weight, convq.bias, padding,
-                                   q_cache, key=(convq.weight.data_ptr(),
-                                                 convq.weight._version))
+                                   q_cache)
             return GruGate2Fn.apply(qp, z, h)
         z, r = torch.sigmoid(zr).chunk(2, dim=1)
         q = torch.tanh(convq(torch.cat([r * h, x], dim=1)))
         return (1 - z) * h + z * q
 
     def forward(self, h, x):
-        if not hasattr(self, "_zr1_cache"):
-            self._zr1_cache, self._zr2_cache = {}, {}
-            self._q1_cache, self._q2_cache = {}, {}
         h = self._pass(h, x, self.convz1, self.convr1, self.convq1, (0, 2),
                        self._zr1_cache, self._q1_cache)  # horizontal
         h = self._pass(h, x, self.convz2, self.convr2, self.convq2, (2, 0),
@@ -147,6 +144,7 @@ class BasicMotionEncoder(nn.Module):
         self.convf1 = FusedConv2d(2, 128, 7, padding=3)
         self.convf2 = FusedConv2d(128, 64, 3, padding=1)
         self.conv = FusedConv2d(64 + 192, 128 - 2, 3, padding=1)
+        self._cv_cache = {}
 
     def forward(self, flow, corr):
         if corr.is_cuda and corr.stride(1) == 1:
@@ -161,13 +159,9 @@ class BasicMotionEncoder(nn.Module):
         if cor.is_cuda and cor.dtype == torch.bfloat16:
             # virtually-concatenated conv input (192 | 64): no cat
             # materialization, no backward narrows
-            if not hasattr(self, "_cv_cache"):
-                self._cv_cache = {}
             out = F.relu(fused_conv2d_cat2(
                 cor, flo, self.conv.weight, self.conv.bias, (1, 1),
-                self._cv_cache,
-                key=(self.conv.weight.data_ptr(),
-                     self.conv.weight._version)))
+                self._cv_cache))
         else:
             out = F.relu(self.conv(torch.cat([cor, flo], dim=1)))
         # keep the motion features in ONE dtype: cat([bf16, fp32]) promotes

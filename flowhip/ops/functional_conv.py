@@ -17,7 +17,7 @@ gradients natively and hands the parameter ONE gradient, from the backward
 of a sink node placed between the parameter and its K uses (WrwSinkFn):
 in one partials buffer reduced once where that measured faster, else by a
 reduce that adds into the running dW (_wrw; the rule sits next to the plan
-code in csrc/conv_gemm.hip).
+code in csrc/conv_gemm.h).
 """
 
 import contextlib
@@ -26,6 +26,7 @@ import threading
 
 import torch
 import torch.nn.functional as F
+from torch.nn.modules.utils import _pair
 
 from . import _ext
 
@@ -56,16 +57,24 @@ def _pad_c8(x, weight):
     return xp, wp
 
 
-def _pad_dy8(dy):
-    """Channel-pad a backward gradient to a multiple of 8 (same OOB-tail
-    argument as _pad_c8; the packed-bwd weight k-columns beyond Cout are
-    zero, so padded dy channels contribute nothing)."""
+def _dy_bf16_cl8(dy):
+    """The backward prologue: dy as bf16, channels-last, channel-padded to
+    a multiple of 8 -> (padded dy, real Cout). Same OOB-tail argument as
+    _pad_c8; the packed-bwd weight k-columns beyond Cout are zero, so
+    padded dy channels contribute nothing."""
+    dy = dy.contiguous(memory_format=torch.channels_last)
+    if dy.dtype != torch.bfloat16:
+        dy = dy.to(torch.bfloat16)
     O = dy.shape[1]
     pad = (-O) % 8
-    if pad == 0:
-        return dy, O
-    z = dy.new_zeros(dy.shape[0], pad, dy.shape[2], dy.shape[3])         .contiguous(memory_format=torch.channels_last)
-    return torch.cat([dy, z], dim=1), O
+    return (_pad_x8(dy, pad) if pad else dy), O
+
+
+def _log_fallback(tag, x, describe):
+    """FLOWHIP_LOG_FALLBACK=1 names every GPU conv that leaves the MFMA
+    path for F.conv2d."""
+    if x.is_cuda and os.environ.get("FLOWHIP_LOG_FALLBACK", "0") == "1":
+        print(f"[{tag} fallback] {describe()}", flush=True)
 
 
 def _pack_fwd(weight):
@@ -89,9 +98,15 @@ def _pack_bwd(weight):
     return F.pad(w, (0, _pad64(O) - O)).contiguous()
 
 
+def _weight_key(*tensors):
+    """Cache key of what is derived from these parameters: changes with an
+    optimizer step (in place, _version) and with a rebound tensor."""
+    return tuple(v for t in tensors for v in (t.data_ptr(), t._version))
+
+
 def _packs(weight, cache, key=None):
     if key is None:
-        key = (weight._version, weight.data_ptr())
+        key = _weight_key(weight)
     if cache.get("k") != key:
         cache["k"] = key
         cache["fwd"] = _pack_fwd(weight)
@@ -165,12 +180,7 @@ class WrwSinkFn(torch.autograd.Function):
         h = ctx.handle
         dw, db = h.dw, h.db
         if h.live:
-            Op, Cin, KH, KW, has_bias = h.geom
-            dw, db = _ext.ext().conv_gemm_wrw_finish(
-                h.buf, Op, Cin, KH, KW, has_bias, h.plan[1], dw,
-                db if has_bias else None)
-            if not has_bias:
-                db = None
+            dw, db = _finish_into_running(h)
         h.buf = h.dw = h.db = None
         h.live = False
         if dw is not None:
@@ -182,6 +192,16 @@ class WrwSinkFn(torch.autograd.Function):
         if gb is not None:
             db = gb if db is None else db + gb
         return None, dw, db
+
+
+def _finish_into_running(h):
+    """Reduce the handle's partials buffer and add the sums to its running
+    (dw, db), made here on the first call -> the new (dw, db)."""
+    Op, Cin, KH, KW, has_bias = h.geom
+    dw, db = _ext.ext().conv_gemm_wrw_finish(
+        h.buf, Op, Cin, KH, KW, has_bias, h.plan[1], h.dw,
+        h.db if has_bias else None)
+    return dw, (db if has_bias else None)
 
 
 def _scope_entry(cache, key, weight, bias, pad8=False):
@@ -247,56 +267,49 @@ def _wrw(handle, dyp, x, x2, KH, KW, sH, sW, has_bias, O_real):
     if accumulate:
         h.live = True
     else:
-        dw, db = E.conv_gemm_wrw_finish(h.buf, geom[0], Cin, KH, KW,
-                                        has_bias, nchunk, h.dw,
-                                        h.db if has_bias else None)
-        h.dw = dw
-        if has_bias:
-            h.db = db
+        h.dw, h.db = _finish_into_running(h)
     return None, None
 
 
 class ConvGemmFn(torch.autograd.Function):
-    """Stride-1 (sH=sW=1) or strided (smode 1 fwd / smode 2 bwd-data)
-    same-padding conv on the MFMA kernel."""
+    """Same-padding conv on the MFMA kernel over x or, with x2 given, over
+    the virtually-concatenated pair cat([x, x2], 1): no per-call cat
+    materialization and no backward narrows (4 per GRU iteration); x's
+    channel count must then be a multiple of 64. Stride 1, or strided
+    (smode 1 fwd / smode 2 bwd-data) with a single source."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, wpk_fwd, wpk_bwd, sH, sW,
+    def forward(ctx, x, x2, weight, bias, wpk_fwd, wpk_bwd, sH, sW,
                 handle=None):
         O, I, KH, KW = weight.shape
         b = bias.detach().float().contiguous() if bias is not None else None
-        if sH == 1 and sW == 1:
-            out = _ext.ext().conv_gemm_fwd(x, wpk_fwd, b, O, KH, KW, 0)
-        else:
-            out = _ext.ext().conv_gemm_fwd2(x, None, wpk_fwd, b, O, KH, KW,
-                                            0, 0, sH, sW, 1)[0]
-        ctx.save_for_backward(x, wpk_bwd)
-        ctx.meta = (O, I, KH, KW, bias is not None, sH, sW)
+        smode = 0 if (sH, sW) == (1, 1) else 1
+        out = _ext.ext().conv_gemm_fwd2(x, x2, wpk_fwd, b, O, KH, KW, 0, 0,
+                                        sH, sW, smode)[0]
+        ctx.save_for_backward(x, x2, wpk_bwd)
+        ctx.meta = (I, KH, KW, bias is not None, sH, sW)
         ctx.handle = handle
         return out
 
     @staticmethod
     def backward(ctx, dy):
-        x, wpk_bwd = ctx.saved_tensors
-        O, I, KH, KW, has_bias, sH, sW = ctx.meta
-        dy = dy.contiguous(memory_format=torch.channels_last)
-        if dy.dtype != torch.bfloat16:
-            dy = dy.to(torch.bfloat16)
-        dyp, O_real = _pad_dy8(dy)
-        dx = None
-        if ctx.needs_input_grad[0]:  # leaf inputs (the stem images) skip dx
-            if sH == 1 and sW == 1:
-                dx = _ext.ext().conv_gemm_fwd(dyp, wpk_bwd, None, I, KH, KW,
-                                              0)
-            else:
-                dx = _ext.ext().conv_gemm_fwd2(dyp, None, wpk_bwd, None, I,
-                                               KH, KW, 0, 0, sH, sW, 2,
-                                               x.shape[2], x.shape[3])[0]
+        x, x2, wpk_bwd = ctx.saved_tensors
+        I, KH, KW, has_bias, sH, sW = ctx.meta
+        dyp, O_real = _dy_bf16_cl8(dy)
+        dx = dx2 = None
+        if x2 is not None:
+            dx, dx2 = _ext.ext().conv_gemm_fwd2(dyp, None, wpk_bwd, None, I,
+                                                KH, KW, x.shape[1], 0)
+        elif ctx.needs_input_grad[0]:  # leaf inputs (the stem images) skip dx
+            smode = 0 if (sH, sW) == (1, 1) else 2
+            dx = _ext.ext().conv_gemm_fwd2(dyp, None, wpk_bwd, None, I, KH,
+                                           KW, 0, 0, sH, sW, smode,
+                                           x.shape[2], x.shape[3])[0]
         dw = dbias = None
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            dw, dbias = _wrw(ctx.handle, dyp, x, None, KH, KW, sH, sW,
+        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
+            dw, dbias = _wrw(ctx.handle, dyp, x, x2, KH, KW, sH, sW,
                              has_bias, O_real)
-        return dx, dw, dbias, None, None, None, None, None
+        return dx, dx2, dw, dbias, None, None, None, None, None
 
 
 def can_fuse_conv(x, weight, stride, padding, dilation, groups):
@@ -306,7 +319,6 @@ def can_fuse_conv(x, weight, stride, padding, dilation, groups):
         return False
     if _ext.ext() is None or _ext.force_ref():
         return False
-    from torch.nn.modules.utils import _pair
     if (_pair(stride) not in ((1, 1), (2, 2))
             or _pair(dilation) != (1, 1) or groups != 1):
         return False
@@ -342,7 +354,7 @@ def fused_conv2d(x, weight, bias, stride, padding, dilation, groups, cache,
             x = xc
     if can_fuse_conv(x, weight, stride, padding, dilation, groups):
         if key is None:
-            key = (weight._version, weight.data_ptr())
+            key = _weight_key(weight)
         # ragged Cin on a tight row: pad both (16-B staging tail).
         # A channel-narrowed view with padded ld (the corr-lookup
         # output) needs NO pad — its tail bytes are in-row and the
@@ -359,49 +371,14 @@ def fused_conv2d(x, weight, bias, stride, padding, dilation, groups, cache,
         elif pad8:
             x, weight = _pad_c8(x, weight)
         wf, wb = _packs(weight, cache, key)
-        from torch.nn.modules.utils import _pair
         sH, sW = _pair(stride)
-        return ConvGemmFn.apply(x, weight, bias, wf, wb, sH, sW, handle)
-    import os
-    if x.is_cuda and os.environ.get("FLOWHIP_LOG_FALLBACK", "0") == "1":
-        print(f"[conv fallback] w={tuple(weight.shape)} stride={stride} "
-              f"pad={padding} dil={dilation} g={groups} x={tuple(x.shape)} "
-              f"xs={x.stride()} dt={x.dtype}", flush=True)
+        return ConvGemmFn.apply(x, None, weight, bias, wf, wb, sH, sW,
+                                handle)
+    _log_fallback("conv", x, lambda: (
+        f"w={tuple(weight.shape)} stride={stride} "
+        f"pad={padding} dil={dilation} g={groups} x={tuple(x.shape)} "
+        f"xs={x.stride()} dt={x.dtype}"))
     return F.conv2d(x, weight, bias, stride, padding, dilation, groups)
-
-
-
-class ConvGemmCat2Fn(torch.autograd.Function):
-    """conv over a virtually-concatenated input pair cat([x1, x2], 1) —
-    removes the per-call cat materialization and its backward narrows
-    (4 per GRU iteration). x1's channel count must be a multiple of 64."""
-
-    @staticmethod
-    def forward(ctx, x1, x2, weight, bias, wpk_fwd, wpk_bwd, handle=None):
-        O, I, KH, KW = weight.shape
-        b = bias.detach().float().contiguous() if bias is not None else None
-        out = _ext.ext().conv_gemm_fwd2(x1, x2, wpk_fwd, b, O, KH, KW, 0,
-                                        0)[0]
-        ctx.save_for_backward(x1, x2, wpk_bwd)
-        ctx.meta = (O, I, KH, KW, bias is not None, x1.shape[1])
-        ctx.handle = handle
-        return out
-
-    @staticmethod
-    def backward(ctx, dy):
-        x1, x2, wpk_bwd = ctx.saved_tensors
-        O, I, KH, KW, has_bias, C1 = ctx.meta
-        dy = dy.contiguous(memory_format=torch.channels_last)
-        if dy.dtype != torch.bfloat16:
-            dy = dy.to(torch.bfloat16)
-        dyp, O_real = _pad_dy8(dy)
-        dx1, dx2 = _ext.ext().conv_gemm_fwd2(dyp, None, wpk_bwd, None, I, KH,
-                                             KW, C1, 0)
-        dw = dbias = None
-        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
-            dw, dbias = _wrw(ctx.handle, dyp, x1, x2, KH, KW, 1, 1,
-                             has_bias, O_real)
-        return dx1, dx2, dw, dbias, None, None, None
 
 
 class ConvGemmCat2ZrFn(torch.autograd.Function):
@@ -427,34 +404,35 @@ class ConvGemmCat2ZrFn(torch.autograd.Function):
     def backward(ctx, dy):
         x1, x2, wpk_bwd = ctx.saved_tensors
         O, Oz, I, KH, KW, C1 = ctx.meta
-        dy = dy.contiguous(memory_format=torch.channels_last)
-        if dy.dtype != torch.bfloat16:
-            dy = dy.to(torch.bfloat16)
+        dy, _ = _dy_bf16_cl8(dy)
         dx1, dx2 = _ext.ext().conv_gemm_fwd2(dy, None, wpk_bwd, None, I, KH,
                                              KW, C1, 0)
         if not any(ctx.needs_input_grad[2:6]):
             return dx1, dx2, None, None, None, None, None, None, None
         dw, db = _ext.ext().conv_gemm_wrw(dy, x1, x2, KH, KW, 1, 1, True)
-        return (dx1, dx2, dw[:Oz], dw[Oz:].contiguous(), db[:Oz],
-                db[Oz:].contiguous(), None, None, None)
+        return (dx1, dx2, dw[:Oz], dw[Oz:O].contiguous(), db[:Oz],
+                db[Oz:O].contiguous(), None, None, None)
+
+
+def _can_fuse_cat2(x1, x2, KH, KW, padding):
+    """Two bf16 channels-last sources on the GPU whose first fills whole
+    64-channel slabs, same padding."""
+    return (x1.is_cuda and x1.dtype == torch.bfloat16
+            and x2.dtype == torch.bfloat16
+            and x1.shape[1] % 64 == 0
+            and (x1.shape[1] + x2.shape[1]) % 8 == 0  # 16-B staging tail
+            and x1.stride(1) == 1 and x2.stride(1) == 1
+            and _ext.ext() is not None and not _ext.force_ref()
+            and _pair(padding) == (KH // 2, KW // 2))
 
 
 def fused_gru_zr_conv(h, x, convz, convr, padding, cache):
     """conv2d(cat([h, x]), cat([wz, wr])) + cat([bz, br]) in one fused
     kernel with version-cached packing. Falls back to the eager
     composition off-GPU."""
-    key = (convz.weight.data_ptr(), convz.weight._version,
-           convr.weight.data_ptr(), convr.weight._version,
-           convz.bias._version, convr.bias._version)
     O1, I, KH, KW = convz.weight.shape
-    fusable = (h.is_cuda and h.dtype == torch.bfloat16
-               and x.dtype == torch.bfloat16
-               and h.shape[1] % 64 == 0
-               and (h.shape[1] + x.shape[1]) % 8 == 0
-               and h.stride(1) == 1 and x.stride(1) == 1
-               and _ext.ext() is not None and not _ext.force_ref())
-    from torch.nn.modules.utils import _pair
-    if fusable and _pair(padding) == (KH // 2, KW // 2):
+    if _can_fuse_cat2(h, x, KH, KW, padding):
+        key = _weight_key(convz.weight, convr.weight, convz.bias, convr.bias)
         if cache.get("k") != key:
             with torch.no_grad():
                 w = torch.cat([convz.weight, convr.weight])
@@ -471,45 +449,37 @@ def fused_gru_zr_conv(h, x, convz, convr, padding, cache):
             # weight cat (and its backward slices) per scope, and the two
             # gates' gradients share one partials buffer
             handle, wh, bh = ent
-            return ConvGemmCat2Fn.apply(h, x, wh, bh, cache["fwd"],
-                                        cache["bwd"], handle)
+            return ConvGemmFn.apply(h, x, wh, bh, cache["fwd"], cache["bwd"],
+                                    1, 1, handle)
         return ConvGemmCat2ZrFn.apply(h, x, convz.weight, convr.weight,
                                       convz.bias, convr.bias, cache["bias"],
                                       cache["fwd"], cache["bwd"])
-    import os
-    if h.is_cuda and os.environ.get("FLOWHIP_LOG_FALLBACK", "0") == "1":
-        print(f"[zr fallback] h={tuple(h.shape)} hd={h.dtype} "
-              f"hs={h.stride()} x={tuple(x.shape)} xd={x.dtype} "
-              f"xs={x.stride()} pad={padding} K=({KH},{KW})", flush=True)
+    _log_fallback("zr", h, lambda: (
+        f"h={tuple(h.shape)} hd={h.dtype} "
+        f"hs={h.stride()} x={tuple(x.shape)} xd={x.dtype} "
+        f"xs={x.stride()} pad={padding} K=({KH},{KW})"))
     zr_w = torch.cat([convz.weight, convr.weight])
     zr_b = torch.cat([convz.bias, convr.bias])
     hx = torch.cat([h, x], dim=1)
     return F.conv2d(hx, zr_w, zr_b, padding=padding)
 
 
-def fused_conv2d_cat2(x1, x2, weight, bias, padding, cache, key):
+def fused_conv2d_cat2(x1, x2, weight, bias, padding, cache, key=None):
     """conv2d(cat([x1, x2], 1), weight) without materializing the cat.
     Falls back to the eager cat + F.conv2d outside the fused envelope."""
     O, I, KH, KW = weight.shape
-    fusable = (x1.is_cuda and x1.dtype == torch.bfloat16
-               and x2.dtype == torch.bfloat16
-               and x1.shape[1] % 64 == 0
-               and (x1.shape[1] + x2.shape[1]) % 8 == 0  # 16-B staging tail
-               and x1.stride(1) == 1 and x2.stride(1) == 1
-               and _ext.ext() is not None and not _ext.force_ref())
-    from torch.nn.modules.utils import _pair
-    if fusable and _pair(padding) == (KH // 2, KW // 2):
+    if _can_fuse_cat2(x1, x2, KH, KW, padding):
+        if key is None:
+            key = _weight_key(weight)
         wf, wb = _packs(weight, cache, key)
         ent = _scope_entry(cache, key, weight, bias)
+        handle = None
         if ent is not None:
-            handle, wh, bh = ent
-            return ConvGemmCat2Fn.apply(x1, x2, wh, bh, wf, wb, handle)
-        return ConvGemmCat2Fn.apply(x1, x2, weight, bias, wf, wb)
-    import os
-    if x1.is_cuda and os.environ.get("FLOWHIP_LOG_FALLBACK", "0") == "1":
-        print(f"[cat2 fallback] x1={tuple(x1.shape)} d={x1.dtype} "
-              f"s={x1.stride()} x2={tuple(x2.shape)} d2={x2.dtype} "
-              f"s2={x2.stride()} w={tuple(weight.shape)} pad={padding}",
-              flush=True)
+            handle, weight, bias = ent
+        return ConvGemmFn.apply(x1, x2, weight, bias, wf, wb, 1, 1, handle)
+    _log_fallback("cat2", x1, lambda: (
+        f"x1={tuple(x1.shape)} d={x1.dtype} "
+        f"s={x1.stride()} x2={tuple(x2.shape)} d2={x2.dtype} "
+        f"s2={x2.stride()} w={tuple(weight.shape)} pad={padding}"))
     hx = torch.cat([x1, x2], dim=1)
     return F.conv2d(hx, weight, bias, padding=padding)

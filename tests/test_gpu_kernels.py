@@ -1022,6 +1022,61 @@ class TestConvGemmCat2:
                                    rtol=5e-2)
 
 
+class TestGruZrConvNoScope:
+    """fused_gru_zr_conv outside a wrw_accumulate_scope (ConvGemmCat2ZrFn:
+    cached packed bias, gradients sliced back to the four parameters)
+    against fp32 F.conv2d of the same bf16-rounded inputs. h 64 + x 192
+    channels -> 2 x 64 gates: 2 x 4 weight-gradient tiles, so dW takes the
+    halo-staged path; 9 x 37 leaves tile tails in both directions."""
+
+    @pytest.mark.parametrize("KH,KW", [(1, 5), (5, 1)], ids=["1x5", "5x1"])
+    def test_matches_cat_conv(self, KH, KW):
+        from flowhip.ops import functional_conv as fc
+        torch.manual_seed(29)
+        B, H, W, CH, CX, O = 2, 9, 37, 64, 192, 64
+        pad = (KH // 2, KW // 2)
+
+        def cl(c):
+            return (torch.randn(B, c, H, W, device=_dev()) / 8) \
+                .to(torch.bfloat16) \
+                .contiguous(memory_format=torch.channels_last) \
+                .requires_grad_(True)
+
+        h, x = cl(CH), cl(CX)
+        convz = torch.nn.Conv2d(CH + CX, O, (KH, KW), padding=pad).to(_dev())
+        convr = torch.nn.Conv2d(CH + CX, O, (KH, KW), padding=pad).to(_dev())
+        with torch.no_grad():
+            for conv in (convz, convr):
+                conv.weight.copy_(torch.randn_like(conv.weight) / 44)
+                conv.bias.copy_(torch.randn_like(conv.bias))
+
+        assert getattr(fc._tls, "handles", None) is None  # no scope open
+        out = fc.fused_gru_zr_conv(h, x, convz, convr, pad, {})
+        assert type(out.grad_fn).__name__ == "ConvGemmCat2ZrFnBackward"
+
+        hr = h.detach().float().requires_grad_(True)
+        xr = x.detach().float().requires_grad_(True)
+        ref_p = [p.detach().clone().requires_grad_(True) for p in
+                 (convz.weight, convr.weight, convz.bias, convr.bias)]
+        ref = torch.nn.functional.conv2d(
+            torch.cat([hr, xr], 1), torch.cat(ref_p[:2]), torch.cat(ref_p[2:]),
+            padding=pad)
+        tol = dict(atol=5e-2, rtol=5e-2)
+        torch.testing.assert_close(out.float(), ref, **tol)
+
+        g = torch.randn_like(ref).to(torch.bfloat16) \
+            .contiguous(memory_format=torch.channels_last)
+        out.backward(g)
+        ref.backward(g.float())
+        torch.testing.assert_close(h.grad.float(), hr.grad, **tol)
+        torch.testing.assert_close(x.grad.float(), xr.grad, **tol)
+        for p, r in zip((convz.weight, convr.weight, convz.bias, convr.bias),
+                        ref_p):
+            assert p.grad.shape == r.grad.shape
+            torch.testing.assert_close(p.grad.float(), r.grad, atol=1e-1,
+                                       rtol=5e-2)
+
+
 class TestAreaUp2x:
     def test_matches_interpolate(self):
         from flowhip import ops
