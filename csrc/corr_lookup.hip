@@ -14,6 +14,16 @@
 // Sampling semantics = grid_sample(align_corners=True, padding_mode=zeros):
 // out-of-range corner pixels contribute zero.
 //
+// Safety: the level coordinate is clamped in float to
+// [-(R+2), extent+R+1] before floorf and the float->int conversion, in the
+// forward and the backward alike (the alt_corr.hip pattern). Outside that
+// band every tap is zero anyway, so in-band results are unchanged, far
+// finite coordinates give zeros as the reference does, and +-inf or NaN
+// (a diverged step) give zeros or NaN. Without the clamp a coordinate
+// >= 2^31 saturates the conversion, `x0 + K` overflows int, the pixel can
+// be classed `interior`, and the unchecked fast path reads (forward) or
+// WRITES (backward) ~2^31 elements past the pixel's map.
+//
 // SEPARABLE-WINDOW FORM: the window offsets are integers, so
 // floor(cx + (a-R)) = floor(cx) + (a-R) and the fractional weights
 // (wx0,wx1,wy0,wy1) are IDENTICAL for all K^2 taps. The 4*K^2 corner
@@ -65,8 +75,11 @@ __global__ __launch_bounds__(LK_THREADS) void corr_lookup_fwd_kernel(
   const int i = pix % P;
 
   const float inv = 1.0f / (float)(1 << l);
-  const float cx = coords[((long)b * 2 + 0) * P + i] * inv;
-  const float cy = coords[((long)b * 2 + 1) * P + i] * inv;
+  float cx = coords[((long)b * 2 + 0) * P + i] * inv;
+  float cy = coords[((long)b * 2 + 1) * P + i] * inv;
+  // clamp BEFORE float->int; fminf/fmaxf also replace NaN by the bound
+  cx = fminf(fmaxf(cx, -(float)(R + 2)), (float)(Wl + R + 1));
+  cy = fminf(fmaxf(cy, -(float)(R + 2)), (float)(Hl + R + 1));
 
   const float fx = floorf(cx), fy = floorf(cy);
   const int x0 = (int)fx - R;  // patch origin
@@ -160,8 +173,11 @@ __global__ __launch_bounds__(LK_THREADS) void corr_lookup_bwd_kernel(
   const int i = pix % P;
 
   const float inv = 1.0f / (float)(1 << l);
-  const float cx = coords[((long)b * 2 + 0) * P + i] * inv;
-  const float cy = coords[((long)b * 2 + 1) * P + i] * inv;
+  float cx = coords[((long)b * 2 + 0) * P + i] * inv;
+  float cy = coords[((long)b * 2 + 1) * P + i] * inv;
+  // clamp BEFORE float->int; fminf/fmaxf also replace NaN by the bound
+  cx = fminf(fmaxf(cx, -(float)(R + 2)), (float)(Wl + R + 1));
+  cy = fminf(fmaxf(cy, -(float)(R + 2)), (float)(Hl + R + 1));
 
   const float fx = floorf(cx), fy = floorf(cy);
   const int x0 = (int)fx - R;

@@ -116,9 +116,19 @@ class CorrLookupFn(torch.autograd.Function):
     CHAIN over the 12 lookups instead of a 12-way fan-out, and each
     backward ACCUMULATES its patch contribution into the incoming level
     grads in-kernel (no per-iteration zero-fill, no autograd add_ fan-in).
-    Callers that drop the passthrough (tests, single lookups) still get
-    correct fan-out semantics: missing chain grads select the fresh-buffer
-    path.
+    The incoming level grads are REUSED IN PLACE: backward writes into them
+    and returns the same tensors — a performance contract of the chain
+    (one buffer per level for the whole loop). That is safe because each
+    passthrough output has exactly one consumer, the next lookup.
+
+    Callers that drop the passthrough (tests, single lookups, the last
+    iteration) still get correct fan-out semantics, by the same path:
+    autograd materialises the undefined level grads as zeros (forward does
+    not call `set_materialize_grads(False)`), so backward accumulates onto
+    fresh zero buffers. The `prev=None` branch below, the binding's own
+    zero-fill plus plain stores, is therefore not reached from autograd; it
+    serves direct callers of `_C.corr_lookup_bwd`.
+    tests/test_gpu_corr_lookup.py pins both down.
     """
 
     @staticmethod
