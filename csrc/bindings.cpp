@@ -10,6 +10,8 @@
 
 // the conv family's geometry, plan and launchers
 #include "conv_gemm.h"
+// the normalized-convolution family's
+#include "nconv.h"
 
 // launchers defined in the other .hip translation units
 void flowhip_bgemm_nt_launch(const void* A, const void* B, void* C,
@@ -47,34 +49,6 @@ void flowhip_convex_up_bwd_launch(const float* gout, const float* flow,
                                   const float* mask, float* gflow,
                                   float* gmask, int N, int H, int W,
                                   int factor, hipStream_t stream);
-void flowhip_nconv_fwd_launch(const float* data, const float* conf,
-                              const float* weight, const float* bias,
-                              float* out, float* cout, int N, int Ci, int Co,
-                              int H, int W, int K, hipStream_t stream);
-void flowhip_nconv_bwd_data_launch(const float* dnomin, const float* ddenom,
-                                   const float* data, const float* conf,
-                                   const float* weight, float* ddata,
-                                   float* dconf, int N, int Ci, int Co, int H,
-                                   int W, int K, hipStream_t stream);
-void flowhip_nconv_wrw_launch(const float* dnomin, const float* ddenom,
-                              const float* data, const float* conf,
-                              float* dweight, int N, int Ci, int Co, int H,
-                              int W, int K, hipStream_t stream);
-int flowhip_nconv_tiled_nblocks(int N, int H, int W, int Ci);
-bool flowhip_nconv_fwd_tiled_launch(const float* data, const float* conf,
-                                    const float* weight, const float* bias,
-                                    float* out, float* cout, int N, int Ci,
-                                    int Co, int H, int W, int K,
-                                    hipStream_t stream);
-bool flowhip_nconv_bwd_data_tiled_launch(
-    const float* dnomin, const float* ddenom, const float* data,
-    const float* conf, const float* weight, float* ddata, float* dconf, int N,
-    int Ci, int Co, int H, int W, int K, hipStream_t stream);
-bool flowhip_nconv_wrw_tiled_launch(const float* dnomin, const float* ddenom,
-                                    const float* data, const float* conf,
-                                    float* partials, float* dweight, int N,
-                                    int Ci, int Co, int H, int W, int K,
-                                    hipStream_t stream);
 int flowhip_instnorm_partial_rows(int N, int C, long P);
 void flowhip_transpose_cast_launch(const void* in, void* out, int B, int M,
                                    int N, int in_bf16, hipStream_t stream);
@@ -132,29 +106,16 @@ void flowhip_seq_loss_bwd_launch(const float* const* preds, float* const* dst,
                                  const float* gloss, long npix, long plane,
                                  float max_flow, float gamma, long numel_full,
                                  hipStream_t stream);
-int flowhip_nconv_bwd_fused_plan(int N, int Ci, int Co, int H, int W, int K,
-                                 int* strip);
-int flowhip_nconv_bwd_fused_ncol(int Ci, int Co, int K);
-bool flowhip_nconv_bwd_fused_launch(
-    const float* gout, const float* gcout, const float* out,
-    const float* cout, const float* data, const float* conf,
-    const float* weight, const float* bias, float* ddata, float* dconf,
-    float* partials, float* dweight, float* dbias, int N, int Ci, int Co,
-    int H, int W, int K, int strip, float eps, hipStream_t stream);
-void flowhip_nconv_bwd_prep_launch(const float* gout, const float* gcout,
-                                   const float* out, const float* cout,
-                                   const float* wsum, const float* bias,
-                                   float* dnomin, float* ddenom, long total,
-                                   long plane, int Co, float eps,
-                                   hipStream_t stream);
 bool flowhip_col_sum2_launch(const void* g, const void* x, float* out,
                              long M, int C, int nchunk,
                              hipStream_t stream);
 void flowhip_frozen_bn_apply_launch(const void* x, void* y, const float* s,
                                     const float* t, long M, int C,
                                     hipStream_t stream);
-void flowhip_plane_dot_sum_launch(const float* x, const float* y, float* out,
-                                  long P, int B, int C, hipStream_t stream);
+int flowhip_plane_dot_sum_pchunks(long P, int B, int C);
+void flowhip_plane_dot_sum_launch(const float* x, const float* y,
+                                  float* partials, float* out, long P, int B,
+                                  int C, hipStream_t stream);
 bool flowhip_col_sum_launch(const void* dy, float* out,
                             long M, int C, int nchunk, hipStream_t stream);
 void flowhip_up2x_cat_fwd_launch(const float* low, const float* skip,
@@ -637,40 +598,66 @@ std::vector<torch::Tensor> convex_up_bwd(torch::Tensor gout,
   return {gflow, gmask};
 }
 
+// The one place a normalized-convolution binding turns its tensors into an
+// NConvGeom: data (N, Ci, H, W) and weight (Co, Ci, K, K) on the device,
+// fp32, contiguous, agreeing on Ci, inside the kernels' envelope.
+#define FLOWHIP_NCONV_ENVELOPE_MSG                                          \
+  ": outside the normalized-convolution kernels' envelope: (K, Ci, Co) "    \
+  "must be an entry of FLOWHIP_NCONV_TABLE (csrc/nconv.h) and W % 4 == 0"
+
+bool nconv_is_plane(const torch::Tensor& t) {
+  return t.is_cuda() && t.is_contiguous() && t.dtype() == torch::kFloat32 &&
+         t.dim() == 4;
+}
+
+NConvGeom nconv_geom(const char* who, const torch::Tensor& data,
+                     const torch::Tensor& weight) {
+  TORCH_CHECK(nconv_is_plane(data) && nconv_is_plane(weight) &&
+                  weight.size(1) == data.size(1) &&
+                  weight.size(3) == weight.size(2),
+              who, ": data (N,Ci,H,W) and weight (Co,Ci,K,K) must be "
+              "contiguous fp32 device tensors");
+  const NConvGeom g{(int)data.size(0),   (int)data.size(1),
+                    (int)weight.size(0), (int)data.size(2),
+                    (int)data.size(3),   (int)weight.size(2)};
+  TORCH_CHECK(flowhip_nconv_launchable(g), who, FLOWHIP_NCONV_ENVELOPE_MSG,
+              "; got K=", g.K, " Ci=", g.Ci, " Co=", g.Co, " W=", g.W);
+  return g;
+}
+
+// t is a (N, C, H, W) plane stack of the layer g
+void nconv_check_planes(const char* who, const NConvGeom& g,
+                        const torch::Tensor& t, int C) {
+  TORCH_CHECK(nconv_is_plane(t) && t.size(0) == g.N && t.size(1) == C &&
+                  t.size(2) == g.H && t.size(3) == g.W,
+              who, ": expected a contiguous fp32 (", g.N, ",", C, ",", g.H,
+              ",", g.W, ") device tensor");
+}
+
+const float* nconv_bias_ptr(const char* who, const NConvGeom& g,
+                            const c10::optional<torch::Tensor>& bias) {
+  if (!bias.has_value()) return nullptr;
+  TORCH_CHECK(bias->is_cuda() && bias->is_contiguous() &&
+                  bias->dtype() == torch::kFloat32 && bias->numel() == g.Co,
+              who, ": bias must be a contiguous fp32 (Co) device tensor");
+  return bias->data_ptr<float>();
+}
+
 std::vector<torch::Tensor> nconv_fwd(torch::Tensor data, torch::Tensor conf,
                                      torch::Tensor weight,
                                      c10::optional<torch::Tensor> bias) {
-  TORCH_CHECK(data.is_cuda() && data.dtype() == torch::kFloat32 &&
-              data.is_contiguous());
-  TORCH_CHECK(conf.is_cuda() && conf.is_contiguous() && conf.sizes() == data.sizes());
-  TORCH_CHECK(weight.is_cuda() && weight.is_contiguous() &&
-              weight.dtype() == torch::kFloat32);
-  const int N = data.size(0), Ci = data.size(1), H = data.size(2),
-            W = data.size(3);
-  const int Co = weight.size(0), K = weight.size(2);
-  TORCH_CHECK(weight.size(1) == Ci && weight.size(3) == K);
-  TORCH_CHECK(Ci <= 8 && Co <= 8 && (K == 1 || K == 3 || K == 5),
-              "nconv_fwd: NCUP configuration space only");
-
-  auto out = torch::empty({N, Co, H, W}, data.options());
-  auto cout = torch::empty({N, Co, H, W}, data.options());
-  const float* bptr = nullptr;
-  if (bias.has_value()) {
-    TORCH_CHECK(bias->is_cuda() && bias->is_contiguous() &&
-                bias->numel() == Co);
-    bptr = bias->data_ptr<float>();
-  }
+  const NConvGeom g = nconv_geom("nconv_fwd", data, weight);
+  nconv_check_planes("nconv_fwd", g, conf, g.Ci);
+  const float* bptr = nconv_bias_ptr("nconv_fwd", g, bias);
+  auto out = torch::empty({g.N, g.Co, g.H, g.W}, data.options());
+  auto cout = torch::empty({g.N, g.Co, g.H, g.W}, data.options());
   const c10::cuda::CUDAGuard guard(data.device());
   hipStream_t stream = at::cuda::getCurrentCUDAStream().stream();
-  if (!flowhip_nconv_fwd_tiled_launch(
-          data.data_ptr<float>(), conf.data_ptr<float>(),
-          weight.data_ptr<float>(), bptr, out.data_ptr<float>(),
-          cout.data_ptr<float>(), N, Ci, Co, H, W, K, stream)) {
-    flowhip_nconv_fwd_launch(data.data_ptr<float>(), conf.data_ptr<float>(),
-                             weight.data_ptr<float>(), bptr,
-                             out.data_ptr<float>(), cout.data_ptr<float>(), N,
-                             Ci, Co, H, W, K, stream);
-  }
+  const bool ok = flowhip_nconv_fwd_launch(
+      data.data_ptr<float>(), conf.data_ptr<float>(),
+      weight.data_ptr<float>(), bptr, out.data_ptr<float>(),
+      cout.data_ptr<float>(), g, stream);
+  TORCH_CHECK(ok, "nconv_fwd: launch refused a checked geometry");
   return {out, cout};
 }
 
@@ -678,59 +665,55 @@ std::vector<torch::Tensor> nconv_bwd(torch::Tensor dnomin,
                                      torch::Tensor ddenom, torch::Tensor data,
                                      torch::Tensor conf,
                                      torch::Tensor weight) {
-  for (auto* t : {&dnomin, &ddenom, &data, &conf, &weight}) {
-    TORCH_CHECK(t->is_cuda() && t->is_contiguous() &&
-                t->dtype() == torch::kFloat32);
-  }
-  const int N = data.size(0), Ci = data.size(1), H = data.size(2),
-            W = data.size(3);
-  const int Co = weight.size(0), K = weight.size(2);
+  const NConvGeom g = nconv_geom("nconv_bwd", data, weight);
+  nconv_check_planes("nconv_bwd", g, conf, g.Ci);
+  nconv_check_planes("nconv_bwd", g, dnomin, g.Co);
+  nconv_check_planes("nconv_bwd", g, ddenom, g.Co);
 
   auto ddata = torch::empty_like(data);
   auto dconf = torch::empty_like(conf);
-  auto dweight = torch::zeros_like(weight);
+  auto dweight = torch::empty_like(weight);
+  auto partials = torch::empty(
+      {flowhip_nconv_wrw_nblocks(g), (long)g.Co * g.Ci * g.K * g.K},
+      data.options());
   const c10::cuda::CUDAGuard guard(data.device());
   hipStream_t stream = at::cuda::getCurrentCUDAStream().stream();
-  if (!flowhip_nconv_bwd_data_tiled_launch(
+  const bool ok =
+      flowhip_nconv_bwd_data_launch(
           dnomin.data_ptr<float>(), ddenom.data_ptr<float>(),
           data.data_ptr<float>(), conf.data_ptr<float>(),
           weight.data_ptr<float>(), ddata.data_ptr<float>(),
-          dconf.data_ptr<float>(), N, Ci, Co, H, W, K, stream)) {
-    flowhip_nconv_bwd_data_launch(
-        dnomin.data_ptr<float>(), ddenom.data_ptr<float>(),
-        data.data_ptr<float>(), conf.data_ptr<float>(),
-        weight.data_ptr<float>(), ddata.data_ptr<float>(),
-        dconf.data_ptr<float>(), N, Ci, Co, H, W, K, stream);
-  }
-  bool wrw_done = false;
-  if (K == 1 || K == 3 || K == 5) {
-    const int nblocks = flowhip_nconv_tiled_nblocks(N, H, W, Ci);
-    auto partials = torch::empty({nblocks, (long)Co * Ci * K * K},
-                                 data.options());
-    wrw_done = flowhip_nconv_wrw_tiled_launch(
-        dnomin.data_ptr<float>(), ddenom.data_ptr<float>(),
-        data.data_ptr<float>(), conf.data_ptr<float>(),
-        partials.data_ptr<float>(), dweight.data_ptr<float>(), N, Ci, Co, H,
-        W, K, stream);
-  }
-  if (!wrw_done) {
-    flowhip_nconv_wrw_launch(
-        dnomin.data_ptr<float>(), ddenom.data_ptr<float>(),
-        data.data_ptr<float>(), conf.data_ptr<float>(),
-        dweight.data_ptr<float>(), N, Ci, Co, H, W, K, stream);
-  }
+          dconf.data_ptr<float>(), g, stream) &&
+      flowhip_nconv_wrw_launch(
+          dnomin.data_ptr<float>(), ddenom.data_ptr<float>(),
+          data.data_ptr<float>(), conf.data_ptr<float>(),
+          partials.data_ptr<float>(), dweight.data_ptr<float>(), g, stream);
+  TORCH_CHECK(ok, "nconv_bwd: launch refused a checked geometry");
   return {ddata, dconf, dweight};
 }
 
+// Elementwise, with no data / weight to take (K, Ci) from, so the table is
+// not consulted here. It refuses W % 4 != 0 only so that no binding of the
+// family accepts planes the others refuse.
 std::vector<torch::Tensor> nconv_bwd_prep(
     torch::Tensor gout, c10::optional<torch::Tensor> gcout, torch::Tensor out,
     torch::Tensor cout, torch::Tensor wsum, c10::optional<torch::Tensor> bias,
     double eps) {
-  TORCH_CHECK(gout.is_cuda() && gout.is_contiguous() &&
-              gout.dtype() == torch::kFloat32);
-  const int Co = gout.size(1);
-  const long plane = (long)gout.size(2) * gout.size(3);
-  const long total = gout.numel();
+  TORCH_CHECK(nconv_is_plane(gout), "nconv_bwd_prep: gout must be a "
+              "contiguous fp32 (N,Co,H,W) device tensor");
+  const NConvGeom g{(int)gout.size(0), 0, (int)gout.size(1),
+                    (int)gout.size(2), (int)gout.size(3), 0};
+  TORCH_CHECK(g.W % 4 == 0, "nconv_bwd_prep: W % 4 == 0 required, as by every "
+              "normalized-convolution binding (the kernel table is not "
+              "checked here: this step sees no K or Ci); got W=", g.W);
+  nconv_check_planes("nconv_bwd_prep", g, out, g.Co);
+  nconv_check_planes("nconv_bwd_prep", g, cout, g.Co);
+  if (gcout.has_value()) nconv_check_planes("nconv_bwd_prep", g, *gcout, g.Co);
+  TORCH_CHECK(wsum.is_cuda() && wsum.is_contiguous() &&
+                  wsum.dtype() == torch::kFloat32 && wsum.numel() == g.Co,
+              "nconv_bwd_prep: wsum must be a contiguous fp32 (Co) device "
+              "tensor");
+  const float* bptr = nconv_bias_ptr("nconv_bwd_prep", g, bias);
   auto dnomin = torch::empty_like(gout);
   auto ddenom = torch::empty_like(gout);
   const c10::cuda::CUDAGuard guard(gout.device());
@@ -739,9 +722,8 @@ std::vector<torch::Tensor> nconv_bwd_prep(
       gout.data_ptr<float>(),
       gcout.has_value() ? gcout->data_ptr<float>() : nullptr,
       out.data_ptr<float>(), cout.data_ptr<float>(), wsum.data_ptr<float>(),
-      bias.has_value() ? bias->data_ptr<float>() : nullptr,
-      dnomin.data_ptr<float>(), ddenom.data_ptr<float>(), total, plane, Co,
-      (float)eps, stream);
+      bptr, dnomin.data_ptr<float>(), ddenom.data_ptr<float>(), gout.numel(),
+      (long)g.H * g.W, g.Co, (float)eps, stream);
   return {dnomin, ddenom};
 }
 
@@ -1382,10 +1364,14 @@ torch::Tensor plane_sum_nchw(torch::Tensor x, c10::optional<torch::Tensor> y) {
   }
   const int B = x.size(0), C = x.size(1);
   const long P = (long)x.size(2) * x.size(3);
-  auto out = torch::zeros({(long)C}, x.options());
+  auto out = torch::empty({(long)C}, x.options());
+  auto partials = torch::empty(
+      {(long)C, (long)B * flowhip_plane_dot_sum_pchunks(P, B, C)},
+      x.options());
   const c10::cuda::CUDAGuard guard(x.device());
   hipStream_t stream = at::cuda::getCurrentCUDAStream().stream();
   flowhip_plane_dot_sum_launch(x.data_ptr<float>(), yp,
+                               partials.data_ptr<float>(),
                                out.data_ptr<float>(), P, B, C, stream);
   return out;
 }
@@ -1605,83 +1591,71 @@ std::vector<torch::Tensor> pacpool_bwd(torch::Tensor dy, torch::Tensor x,
 // {ddata, dconf, dweight, dbias (empty without bias)}.
 // algo 1: the fused kernel of nconv_bwd_fused.hip (one pass + reduce);
 // algo 0: the split path (prep, bwd-data, wrw + reduce, plane sums and the
-// torch glue between them); algo -1: fused inside its envelope, else split.
-// gout or gcout may be absent (treated as zeros), not both.
+// torch glue between them); algo -1: automatic, which is fused — the two
+// paths share one envelope. gout or gcout may be absent (treated as zeros),
+// not both.
 std::vector<torch::Tensor> nconv_bwd_fused(
     c10::optional<torch::Tensor> gout, c10::optional<torch::Tensor> gcout,
     torch::Tensor out, torch::Tensor cout, torch::Tensor data,
     torch::Tensor conf, torch::Tensor weight,
     c10::optional<torch::Tensor> bias, double eps, int64_t algo,
     int64_t strip) {
+  const char* who = "nconv_bwd_fused";
   TORCH_CHECK(algo >= -1 && algo <= 1, "nconv_bwd_fused: algo must be -1, 0, 1");
   TORCH_CHECK(gout.has_value() || gcout.has_value(),
               "nconv_bwd_fused: no upstream gradient");
-  for (auto* t : {&out, &cout, &data, &conf, &weight}) {
-    TORCH_CHECK(t->is_cuda() && t->is_contiguous() &&
-                t->dtype() == torch::kFloat32);
-  }
-  for (auto* t : {&gout, &gcout}) {
-    TORCH_CHECK(!t->has_value() ||
-                ((*t)->is_cuda() && (*t)->is_contiguous() &&
-                 (*t)->dtype() == torch::kFloat32 &&
-                 (*t)->sizes() == out.sizes()));
-  }
-  TORCH_CHECK(data.dim() == 4 && conf.sizes() == data.sizes() &&
-              cout.sizes() == out.sizes() && weight.dim() == 4);
-  const int N = data.size(0), Ci = data.size(1), H = data.size(2),
-            W = data.size(3);
-  const int Co = weight.size(0), K = weight.size(2);
-  TORCH_CHECK(weight.size(1) == Ci && weight.size(3) == K &&
-              out.size(0) == N && out.size(1) == Co && out.size(2) == H &&
-              out.size(3) == W);
-  if (bias.has_value())
-    TORCH_CHECK(bias->is_cuda() && bias->is_contiguous() &&
-                bias->dtype() == torch::kFloat32 && bias->numel() == Co);
+  const NConvGeom g = nconv_geom(who, data, weight);
+  nconv_check_planes(who, g, conf, g.Ci);
+  nconv_check_planes(who, g, out, g.Co);
+  nconv_check_planes(who, g, cout, g.Co);
+  if (gout.has_value()) nconv_check_planes(who, g, *gout, g.Co);
+  if (gcout.has_value()) nconv_check_planes(who, g, *gcout, g.Co);
+  const float* bptr = nconv_bias_ptr(who, g, bias);
 
-  int st = (int)strip;
-  const int nblocks = flowhip_nconv_bwd_fused_plan(N, Ci, Co, H, W, K, &st);
-  TORCH_CHECK(algo != 1 || nblocks > 0,
-              "nconv_bwd_fused: algo=1 forced on a shape outside the fused "
-              "envelope (K in {1,3,5}, tiled (Ci,Co) pairs, W % 4 == 0)");
   const c10::cuda::CUDAGuard guard(data.device());
-  if (algo != 0 && nblocks > 0) {
+  if (algo != 0) {
+    int st = (int)strip;
+    const int nblocks = flowhip_nconv_bwd_fused_plan(g, &st);
     auto ddata = torch::empty_like(data);
     auto dconf = torch::empty_like(conf);
     auto dweight = torch::empty_like(weight);
-    auto dbias = torch::empty({bias.has_value() ? (long)Co : 0L},
+    auto dbias = torch::empty({bias.has_value() ? (long)g.Co : 0L},
                               data.options());
     auto partials = torch::empty(
-        {nblocks, (long)flowhip_nconv_bwd_fused_ncol(Ci, Co, K)},
-        data.options());
+        {nblocks, (long)flowhip_nconv_bwd_fused_ncol(g)}, data.options());
     hipStream_t stream = at::cuda::getCurrentCUDAStream().stream();
     const bool ok = flowhip_nconv_bwd_fused_launch(
         gout.has_value() ? gout->data_ptr<float>() : nullptr,
         gcout.has_value() ? gcout->data_ptr<float>() : nullptr,
         out.data_ptr<float>(), cout.data_ptr<float>(),
         data.data_ptr<float>(), conf.data_ptr<float>(),
-        weight.data_ptr<float>(),
-        bias.has_value() ? bias->data_ptr<float>() : nullptr,
-        ddata.data_ptr<float>(), dconf.data_ptr<float>(),
-        partials.data_ptr<float>(), dweight.data_ptr<float>(),
-        bias.has_value() ? dbias.data_ptr<float>() : nullptr, N, Ci, Co, H, W,
-        K, st, (float)eps, stream);
-    TORCH_CHECK(ok, "nconv_bwd_fused: launch refused a planned shape");
+        weight.data_ptr<float>(), bptr, ddata.data_ptr<float>(),
+        dconf.data_ptr<float>(), partials.data_ptr<float>(),
+        dweight.data_ptr<float>(),
+        bias.has_value() ? dbias.data_ptr<float>() : nullptr, g, st,
+        (float)eps, stream);
+    TORCH_CHECK(ok, "nconv_bwd_fused: launch refused a checked geometry");
     return {ddata, dconf, dweight, dbias};
   }
 
-  // split path, as NConv2dFn.backward composed it
+  // split path: the kernels the fused one replaced, and their torch glue
   auto s = weight.sum(at::IntArrayRef({1, 2, 3})).contiguous();
   auto go = gout.has_value() ? *gout : torch::zeros_like(out);
   auto pre = nconv_bwd_prep(go, gcout, out, cout, s, bias, eps);
   auto r = nconv_bwd(pre[0], pre[1], data, conf, weight);
   auto dweight = r[2];
   if (gcout.has_value()) {
+    // cout = denom / s depends on s = sum(w) per out channel
     auto ds = -plane_sum_nchw(cout, *gcout) / s;
     dweight = dweight + ds.view({-1, 1, 1, 1});
   }
   auto dbias = bias.has_value() ? plane_sum_nchw(go, c10::nullopt)
                                 : torch::empty({0}, data.options());
   return {r[0], r[1], dweight, dbias};
+}
+
+bool nconv_supported(int64_t Ci, int64_t Co, int64_t K) {
+  return flowhip_nconv_supported((int)Ci, (int)Co, (int)K);
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1810,6 +1784,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused elementwise preamble of nconv backward (dnomin, ddenom)");
   m.def("nconv_bwd", &nconv_bwd,
         "fused normalized convolution backward (ddata, dconf, dweight)");
+  m.def("nconv_supported", &nconv_supported,
+        "is (Ci, Co, K) an entry of the normalized-convolution kernel table",
+        py::arg("Ci"), py::arg("Co"), py::arg("K"));
   m.def("nconv_bwd_fused", &nconv_bwd_fused,
         "whole nconv layer backward -> (ddata, dconf, dweight, dbias); "
         "algo 0 = split kernels, 1 = fused kernel, -1 = automatic",

@@ -127,9 +127,12 @@ __global__ __launch_bounds__(CS_THREADS) void col_sum2_partial_kernel(
 // Per-channel plane reduction on NCHW fp32: out[c] = sum_{b,h,w} x (or
 // x*y). Replaces the eager mul+sum pair in the nconv backward's
 // ds-through-sum(w) term (full-res (B,2,H,W) tensors, ~48 pairs/step).
+// Two stages, no atomics, so the result repeats bit for bit: block
+// (b, c, chunk) writes its sum to partials[c][b * pchunks + chunk], and
+// plane_dot_sum_finish_kernel adds a channel's parts in a fixed order.
 __global__ __launch_bounds__(256) void plane_dot_sum_kernel(
     const float* __restrict__ x, const float* __restrict__ y,
-    float* __restrict__ out, long P, int C, int pchunks) {
+    float* __restrict__ partials, long P, int C, int pchunks) {
   const int bc = blockIdx.x;
   const int c = bc % C;
   const int chunk = blockIdx.y;
@@ -166,19 +169,51 @@ __global__ __launch_bounds__(256) void plane_dot_sum_kernel(
     if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
     __syncthreads();
   }
-  if (threadIdx.x == 0) atomicAdd(&out[c], red[0]);
+  if (threadIdx.x == 0) {
+    const int nparts = (int)(gridDim.x / C) * pchunks;
+    partials[(long)c * nparts + (bc / C) * pchunks + chunk] = red[0];
+  }
 }
 
-void flowhip_plane_dot_sum_launch(const float* x, const float* y, float* out,
-                                  long P, int B, int C, hipStream_t stream) {
+// out[c] = sum of partials[c][0 .. nparts). One workgroup per channel.
+__global__ __launch_bounds__(256) void plane_dot_sum_finish_kernel(
+    const float* __restrict__ partials, float* __restrict__ out, int nparts) {
+  const float* pc = partials + (long)blockIdx.x * nparts;
+  float acc = 0.f;
+  for (int i = threadIdx.x; i < nparts; i += 256) acc += pc[i];
+  __shared__ float red[256];
+  red[threadIdx.x] = acc;
+  __syncthreads();
+#pragma unroll
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[blockIdx.x] = red[0];
+}
+
+// Chunks each (b, c) plane is split into: enough blocks to fill the chip,
+// at least 1024 elements each.
+int flowhip_plane_dot_sum_pchunks(long P, int B, int C) {
   int pchunks = (int)((512 + (long)B * C - 1) / ((long)B * C));
   if (pchunks < 1) pchunks = 1;
   if (pchunks > 1024) pchunks = 1024;
   if ((long)pchunks > (P + 1023) / 1024) pchunks = (int)((P + 1023) / 1024);
   if (pchunks < 1) pchunks = 1;
+  return pchunks;
+}
+
+// partials: C * B * flowhip_plane_dot_sum_pchunks(P, B, C) floats, all
+// written before they are read.
+void flowhip_plane_dot_sum_launch(const float* x, const float* y,
+                                  float* partials, float* out, long P, int B,
+                                  int C, hipStream_t stream) {
+  const int pchunks = flowhip_plane_dot_sum_pchunks(P, B, C);
   dim3 grid(B * C, pchunks), block(256);
-  hipLaunchKernelGGL(plane_dot_sum_kernel, grid, block, 0, stream, x, y, out,
-                     P, C, pchunks);
+  hipLaunchKernelGGL(plane_dot_sum_kernel, grid, block, 0, stream, x, y,
+                     partials, P, C, pchunks);
+  hipLaunchKernelGGL(plane_dot_sum_finish_kernel, dim3(C), block, 0, stream,
+                     partials, out, B * pchunks);
 }
 
 // Frozen-BN affine: y[m,c] = bf16(fp32(x[m,c]) * s[c] + t[c]) on

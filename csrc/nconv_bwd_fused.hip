@@ -1,7 +1,7 @@
 // Fused normalized-convolution backward: one pass over the planes of a
 // layer produces ddata, dconf and the per-workgroup partials of dweight /
 // dbias; a small reduce kernel finishes them. Replaces the prep, bwd-data,
-// wrw(+reduce) and plane-dot kernels of nconv_tiled.hip and the torch glue
+// wrw(+reduce) and plane-dot kernels of nconv.hip and the torch glue
 // around them (math contract: header of flowhip/ops/functional_nconv.py).
 //
 //   de     = cout * s[co] + eps,  s[co] = sum(w[co])   (denom from cout)
@@ -26,10 +26,11 @@
 #include <type_traits>
 
 #include "common.h"
+#include "nconv.h"
 
 #define NBF_THREADS 256
-#define NBF_TW 64
-#define NBF_TH 16
+#define NBF_TW NCONV_TW
+#define NBF_TH NCONV_TH
 
 // LDS row stride: halo row rounded up to whole float4s, so the row reads
 // are 16-B aligned.
@@ -430,71 +431,33 @@ __global__ __launch_bounds__(NBF_THREADS) void nconv_bwd_fused_reduce_kernel(
 }
 
 // ---------------------------------------------------------------------------
-// Launchers. The (K, Ci, Co) space is the tiled forward's; anything else,
-// or W % 4 != 0, is outside the envelope (plan returns 0, launch false)
-// and the caller keeps the split kernels.
+// Launcher. The envelope is the family's (flowhip_nconv_launchable, nconv.h);
+// outside it the plan is 0 rows and nothing is launched.
 // ---------------------------------------------------------------------------
-
-#define NBF_FOR_ALL(X)                                                      \
-  X(5, 1, 1) X(5, 1, 2) X(5, 1, 4) X(5, 2, 1) X(5, 2, 2) X(5, 2, 4)         \
-  X(5, 4, 2) X(5, 4, 4)                                                     \
-  X(3, 1, 1) X(3, 1, 2) X(3, 1, 4) X(3, 2, 1) X(3, 2, 2) X(3, 2, 4)         \
-  X(3, 4, 2) X(3, 4, 4) X(3, 8, 2)                                          \
-  X(1, 1, 1) X(1, 1, 2) X(1, 2, 1) X(1, 2, 2) X(1, 4, 2)
-
-static bool nbf_covers(int Ci, int Co, int K) {
-#define NBF_CASE_COVERS(KK, CIV, COV) \
-  if (K == KK && Ci == CIV && Co == COV) return true;
-  NBF_FOR_ALL(NBF_CASE_COVERS)
-  return false;
-}
-
-// Number of workgroups (= partials rows) of the fused launch, 0 outside
-// the envelope. strip <= 0 picks the strip length: about 384 workgroups
-// (1.5 per CU) when the image has that many tiles. Shorter strips pay the
-// per-workgroup reduction more often, longer ones leave CUs idle
-// (bench_nconv_bwd.py --strips: 4 / 7 / 14 tile rows at the flagship).
-int flowhip_nconv_bwd_fused_plan(int N, int Ci, int Co, int H, int W, int K,
-                                 int* strip) {
-  if (W % 4 != 0 || !nbf_covers(Ci, Co, K)) return 0;
-  const int ntx = fh_cdiv(W, NBF_TW), nty = fh_cdiv(H, NBF_TH);
-  int st = *strip;
-  if (st <= 0) {
-    st = (ntx * nty * N) / 384;
-    if (st < 1) st = 1;
-    if (st > 8) st = 8;
-  }
-  if (st > nty) st = nty;
-  *strip = st;
-  return ntx * fh_cdiv(nty, st) * N;
-}
-
-int flowhip_nconv_bwd_fused_ncol(int Ci, int Co, int K) {
-  return Co * Ci * K * K + 2 * Co;
-}
 
 bool flowhip_nconv_bwd_fused_launch(
     const float* gout, const float* gcout, const float* out,
     const float* cout, const float* data, const float* conf,
     const float* weight, const float* bias, float* ddata, float* dconf,
-    float* partials, float* dweight, float* dbias, int N, int Ci, int Co,
-    int H, int W, int K, int strip, float eps, hipStream_t stream) {
-  const int nblocks = flowhip_nconv_bwd_fused_plan(N, Ci, Co, H, W, K, &strip);
+    float* partials, float* dweight, float* dbias, const NConvGeom& g,
+    int strip, float eps, hipStream_t stream) {
+  const int nblocks = flowhip_nconv_bwd_fused_plan(g, &strip);
   if (nblocks == 0) return false;
-  const int ntx = fh_cdiv(W, NBF_TW), nty = fh_cdiv(H, NBF_TH);
+  const int ntx = fh_cdiv(g.W, NBF_TW), nty = fh_cdiv(g.H, NBF_TH);
   const int nstrips = fh_cdiv(nty, strip);
   dim3 grid(nblocks), block(NBF_THREADS);
 #define NBF_CASE_LAUNCH(KK, CIV, COV)                                        \
-  if (K == KK && Ci == CIV && Co == COV)                                     \
+  if (g.K == KK && g.Ci == CIV && g.Co == COV)                               \
     hipLaunchKernelGGL((nconv_bwd_fused_kernel<KK, CIV, COV>), grid, block,  \
                        0, stream, gout, gcout, out, cout, data, conf,        \
-                       weight, bias, ddata, dconf, partials, H, W, ntx, nty, \
-                       strip, nstrips, eps);
-  NBF_FOR_ALL(NBF_CASE_LAUNCH)
-  const int NW = Ci * K * K;
+                       weight, bias, ddata, dconf, partials, g.H, g.W, ntx,  \
+                       nty, strip, nstrips, eps);
+  FLOWHIP_NCONV_TABLE(NBF_CASE_LAUNCH)
+#undef NBF_CASE_LAUNCH
+  const int NW = g.Ci * g.K * g.K;
   hipLaunchKernelGGL(nconv_bwd_fused_reduce_kernel,
-                     dim3(Co * NW + (bias != nullptr ? Co : 0)),
+                     dim3(g.Co * NW + (bias != nullptr ? g.Co : 0)),
                      dim3(NBF_THREADS), 0, stream, partials, weight, dweight,
-                     dbias, nblocks, NW, Co, gcout != nullptr ? 1 : 0);
+                     dbias, nblocks, NW, g.Co, gcout != nullptr ? 1 : 0);
   return true;
 }

@@ -127,8 +127,9 @@ class NConv2d(nn.Module):
             return None
         weight = self.weight
         folded = weight[:, :m] + weight[:, m:]
-        if not ops.nconv2d_uses_hip(data, folded, self.stride, self.dilation,
-                                    self.groups):
+        if not ops.nconv2d_uses_hip(
+                data, conf, folded, self.stride, self.padding, self.dilation,
+                self.groups, self.eps, self.prop_conf):
             return None
         return ops.nconv2d(
             data, conf, folded, self.bias, self.stride, self.padding,

@@ -133,25 +133,45 @@ def alt_corr_lookup(fmap1, fmap2_levels, coords, radius, fmap2=None,
 
 def nconv2d(data, conf, weight, bias=None, stride=1, padding=0, dilation=1,
             groups=1, eps=1e-20, prop_conf=True):
-    if _ext.use_hip(data) and _can_fuse_nconv(weight, stride, dilation, groups):
+    if _ext.use_hip(data) and _can_fuse_nconv(
+            data, conf, weight, stride, padding, dilation, groups, eps,
+            prop_conf, warn=True):
         from .functional_nconv import NConv2dFn
         return NConv2dFn.apply(data, conf, weight, bias, padding, eps, prop_conf)
     return torch_ref.nconv2d(data, conf, weight, bias, stride, padding,
                              dilation, groups, eps, prop_conf)
 
 
-def nconv2d_uses_hip(data, weight, stride=1, dilation=1, groups=1):
+def nconv2d_uses_hip(data, conf, weight, stride=1, padding=0, dilation=1,
+                     groups=1, eps=1e-20, prop_conf=True):
     """True where nconv2d would run the HIP kernels for these arguments."""
-    return _ext.use_hip(data) and _can_fuse_nconv(weight, stride, dilation,
-                                                  groups)
+    return _ext.use_hip(data) and _can_fuse_nconv(
+        data, conf, weight, stride, padding, dilation, groups, eps, prop_conf)
 
 
-def _can_fuse_nconv(weight, stride, dilation, groups):
+def _can_fuse_nconv(data, conf, weight, stride, padding, dilation, groups,
+                    eps, prop_conf, warn=False):
+    """Everything the kernels hard-wire — stride 1, dilation 1, groups 1,
+    square K, zero padding K//2, the forward's eps of 1e-20, propagated
+    confidence, fp32 — and their (Ci, Co, K) table. `warn` reports a call
+    that only the table keeps on the torch path."""
     from torch.nn.modules.utils import _pair
     if _pair(stride) != (1, 1) or _pair(dilation) != (1, 1) or groups != 1:
         return False
     o, i, kh, kw = weight.shape
-    return kh == kw and kh in (1, 3, 5) and i <= 8 and o <= 8
+    if (kh != kw or _pair(padding) != (kh // 2, kh // 2) or eps != 1e-20
+            or not prop_conf
+            or not data.dtype == conf.dtype == weight.dtype == torch.float32):
+        return False
+    if _ext.ext().nconv_supported(i, o, kh):
+        return True
+    if warn:
+        import warnings
+        warnings.warn(
+            f"nconv2d: (Ci, Co, K) = ({i}, {o}, {kh}) is not in the "
+            "normalized-convolution kernel table (csrc/nconv.h); using the "
+            "torch path")
+    return False
 
 
 def conf_pool(data, conf, ds_factor=2, pooling_type="conf_based"):

@@ -1,14 +1,19 @@
-"""Autograd binding for the fused normalized-convolution kernel.
+"""Autograd binding for the fused normalized-convolution kernels.
 
 Forward: one fused HIP kernel (csrc/nconv.hip) producing (nconv, cout).
 Backward: one fused HIP kernel plus a small reduce
-(csrc/nconv_bwd_fused.hip) producing ddata, dconf, dweight and dbias; shapes
-outside its envelope, and FLOWHIP_NCONV_BWD=split, take the split kernels
-(prep, bwd-data, weight-grad, plane sums) with their torch glue. denom is
-reconstructed from the saved cout (denom = cout * sum(w)) so no extra
+(csrc/nconv_bwd_fused.hip) producing ddata, dconf, dweight and dbias;
+FLOWHIP_NCONV_BWD=split (read per call) runs the split kernels (prep,
+bwd-data, weight-grad, plane sums) through the same binding instead. denom
+is reconstructed from the saved cout (denom = cout * sum(w)) so no extra
 forward tensor is stored. (The original torch/MIOpen composition fell into
 naive_conv wrw fallbacks at ~240 ms/call for these tiny-channel full-res
 shapes — see profiles/.)
+
+The kernels need whole float4 rows. At W % 4 != 0 the planes are
+right-padded with zero columns to the next multiple of 4 and the results
+sliced back: the convolution zero-pads outside the image anyway, and pad
+columns with zero upstream gradient add nothing to dweight or dbias.
 
 Math (d denotes upstream grads):
   nomin = (out − bias) · (denom + eps)
@@ -25,13 +30,22 @@ Reference math: nconv_modules.py:164-199.
 import os
 
 import torch
+import torch.nn.functional as F
 
 from . import _ext
 
 
 class NConv2dFn(torch.autograd.Function):
+    """padding, eps and prop_conf are what ops.nconv2d admitted: K // 2,
+    1e-20 and True, the values the kernels hard-wire."""
+
     @staticmethod
     def forward(ctx, data, conf, weight, bias, padding, eps, prop_conf):
+        W = data.shape[-1]
+        pad = -W % 4
+        if pad:
+            data = F.pad(data, (0, pad))
+            conf = F.pad(conf, (0, pad))
         data = data.contiguous()
         conf = conf.contiguous()
         weight = weight.contiguous()
@@ -42,11 +56,13 @@ class NConv2dFn(torch.autograd.Function):
         else:
             ctx.save_for_backward(data, conf, weight, out, cout)
         ctx.has_bias = bias is not None
-        ctx.padding = padding
         ctx.eps = eps
+        ctx.pad = pad
         # an unused output (the cout dropped after nconv_out) then arrives
         # in backward as None instead of a zero-filled plane
         ctx.set_materialize_grads(False)
+        if pad:
+            return out[..., :W].contiguous(), cout[..., :W].contiguous()
         return out, cout
 
     @staticmethod
@@ -55,45 +71,24 @@ class NConv2dFn(torch.autograd.Function):
             return None, None, None, None, None, None, None
         data, conf, weight, out, cout, *maybe_bias = ctx.saved_tensors
         bias = maybe_bias[0] if ctx.has_bias else None
+        if ctx.pad:
+            gout = F.pad(gout, (0, ctx.pad)) if gout is not None else None
+            gcout = F.pad(gcout, (0, ctx.pad)) if gcout is not None else None
         gout = gout.contiguous() if gout is not None else None
         gcout = gcout.contiguous() if gcout is not None else None
 
-        if os.environ.get("FLOWHIP_NCONV_BWD", "") == "split":
-            ddata, dconf, dweight, dbias = _backward_split(
-                gout, gcout, out, cout, data, conf, weight, bias, ctx.eps)
-        else:
-            ddata, dconf, dweight, dbias = _ext.ext().nconv_bwd_fused(
-                gout, gcout, out, cout, data, conf, weight, bias, ctx.eps, -1)
+        algo = 0 if os.environ.get("FLOWHIP_NCONV_BWD", "") == "split" else -1
+        ddata, dconf, dweight, dbias = _ext.ext().nconv_bwd_fused(
+            gout, gcout, out, cout, data, conf, weight, bias, ctx.eps, algo)
+        if ctx.pad:
+            W = data.shape[-1] - ctx.pad
+            ddata = ddata[..., :W].contiguous()
+            dconf = dconf[..., :W].contiguous()
         if not ctx.needs_input_grad[2]:
             dweight = None
         if not ctx.has_bias:
             dbias = None
         return ddata, dconf, dweight, dbias, None, None, None
-
-
-def _backward_split(gout, gcout, out, cout, data, conf, weight, bias, eps):
-    """The pre-fusion backward: prep, bwd-data, weight-grad and plane-sum
-    kernels with the glue between them in torch ops."""
-    s = weight.sum(dim=(1, 2, 3)).contiguous()         # (Co)
-    if gout is None:
-        gout = torch.zeros_like(out)
-
-    # fused elementwise preamble (one kernel): denom reconstructed from
-    # cout; dnomin = gout/de, ddenom = -gout*(out-bias)/de + gcout/s
-    dnomin, ddenom = _ext.ext().nconv_bwd_prep(
-        gout, gcout, out, cout, s, bias, eps)
-
-    ddata, dconf, dweight = _ext.ext().nconv_bwd(dnomin, ddenom, data,
-                                                 conf, weight)
-    if gcout is not None:
-        # cout = denom/s depends on s = sum(w) per out channel; one
-        # fused per-channel plane reduction instead of the full-res
-        # mul + sum pair
-        ds = -_ext.ext().plane_sum_nchw(cout, gcout) / s
-        dweight = dweight + ds.view(-1, 1, 1, 1)
-
-    dbias = _ext.ext().plane_sum_nchw(gout) if bias is not None else None
-    return ddata, dconf, dweight, dbias
 
 
 class ConfPoolFn(torch.autograd.Function):

@@ -13,13 +13,22 @@ Shapes (N=2): 5x8 is smaller than a tile and than the 5x5 halo reach, so
 every staged chunk crosses an image edge; 19x68 has a 4-wide tile tail in x
 and a 3-row tail in y; 37x132 has three tile columns and three tile rows
 (forced strip lengths 1 and 2 give several strips with a ragged last one);
-18x22 has W % 4 != 0 and must take the split kernels through algo=-1.
+18x22 has W % 4 != 0: the bindings refuse it, and run it zero-padded to
+18x24 with zero upstream gradient in the pad columns, which is the same
+problem in columns [0, 22) (asserted on the fp64 reference before anything
+runs on the GPU).
+
+Further down: NConv2dFn at unaligned widths (it pads and slices), an
+off-table layer through ops.nconv2d (torch path, with a warning), and
+FLOWHIP_NCONV_BWD=split.
 """
 
 import os
+import warnings
 
 import pytest
 import torch
+import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
@@ -53,12 +62,42 @@ def _id(c):
 _cache = {}
 
 
+def _ref64(data, conf, weight, bias, gout, gcout, k, need_samples=True):
+    """fp64 outputs and gradients of torch_ref.nconv2d on the CPU, with and
+    without gcout."""
+    from flowhip.ops import torch_ref
+    refs = {}
+    for with_gcout in (True, False):
+        leaves = [t.double().requires_grad_(True)
+                  for t in (data, conf, weight)]
+        b64 = bias.double().requires_grad_(True) if bias is not None else None
+        rout, rcout = torch_ref.nconv2d(leaves[0], leaves[1], leaves[2], b64,
+                                        1, k // 2, 1, 1, EPS, True)
+        if need_samples:
+            assert (rcout > 0).all(), "a window without samples: no reference"
+        outs, grads = [rout], [gout.double()]
+        if with_gcout:
+            outs.append(rcout)
+            grads.append(gcout.double())
+        wrt = leaves + ([b64] if bias is not None else [])
+        r = torch.autograd.grad(outs, wrt, grads)
+        refs[with_gcout] = dict(out=rout.detach(), cout=rcout.detach(),
+                                ddata=r[0], dconf=r[1], dweight=r[2],
+                                dbias=r[3] if bias is not None else None)
+    return refs
+
+
+def _rpad(t, pad):
+    """t with `pad` zero columns appended on the right."""
+    return F.pad(t, (0, pad)) if pad else t
+
+
 def _case(case):
-    """Inputs, the kernel's own forward outputs and the fp64 gradients with
-    and without gcout, built once per case."""
+    """Inputs (right-padded with zero columns to W % 4 == 0), the kernel's
+    own forward outputs on them and the fp64 gradients of the unpadded
+    problem with and without gcout, built once per case."""
     if case in _cache:
         return _cache[case]
-    from flowhip.ops import torch_ref
     import flowhip._C as C
     ci, co, k, has_bias, H, W, inject = case
     N = 2
@@ -76,22 +115,24 @@ def _case(case):
     gout = torch.randn(N, co, H, W, generator=g)
     gcout = torch.randn(N, co, H, W, generator=g)
 
-    refs = {}
-    for with_gcout in (True, False):
-        leaves = [t.double().requires_grad_(True)
-                  for t in (data, conf, weight)]
-        b64 = bias.double().requires_grad_(True) if has_bias else None
-        rout, rcout = torch_ref.nconv2d(leaves[0], leaves[1], leaves[2], b64,
-                                        1, k // 2, 1, 1, EPS, True)
-        assert (rcout > 0).all(), "a window without samples: no reference"
-        outs, grads = [rout], [gout.double()]
-        if with_gcout:
-            outs.append(rcout)
-            grads.append(gcout.double())
-        wrt = leaves + ([b64] if has_bias else [])
-        r = torch.autograd.grad(outs, wrt, grads)
-        refs[with_gcout] = dict(ddata=r[0], dconf=r[1], dweight=r[2],
-                                dbias=r[3] if has_bias else None)
+    refs = _ref64(data, conf, weight, bias, gout, gcout, k)
+    pad = -W % 4
+    if pad:
+        # on the CPU, before the GPU sees the padded problem: it is the
+        # unpadded one in columns [0, W)
+        data, conf, gout, gcout = (_rpad(t, pad)
+                                   for t in (data, conf, gout, gcout))
+        prefs = _ref64(data, conf, weight, bias, gout, gcout, k,
+                       need_samples=False)
+        for with_gcout in (True, False):
+            for name, r in refs[with_gcout].items():
+                if r is None:
+                    continue
+                pr = prefs[with_gcout][name]
+                assert torch.isfinite(pr).all(), name
+                if name not in ("dweight", "dbias"):
+                    pr = pr[..., :W]
+                assert (pr - r).abs().max().item() <= 1e-10, name
 
     dv = _dev()
     t = dict(data=data.to(dv), conf=conf.to(dv), weight=weight.to(dv),
@@ -120,34 +161,35 @@ def test_fused_vs_split_vs_fp64(case, with_gcout):
     ci, co, k, has_bias, H, W, inject = case
     t, refs = _case(case)
     ref = refs[with_gcout]
-    fusable = W % 4 == 0
     split = _run(t, with_gcout, 0)
-    # outside the envelope the automatic rule must take the split kernels
-    fused = _run(t, with_gcout, 1 if fusable else -1)
+    fused = _run(t, with_gcout, 1)
     for name in ("ddata", "dconf", "dweight", "dbias"):
         if ref[name] is None:
             continue
         r = ref[name]
         s = split[name].double().cpu()
         f = fused[name].double().cpu()
+        if name in ("ddata", "dconf"):  # the image's columns of a padded run
+            s, f = s[..., :W], f[..., :W]
         err_s = (s - r).abs().max().item()
         err_f = (f - r).abs().max().item()
         print(f"[nconv_bwd_fused] {_id(case)} "
               f"{'gcout' if with_gcout else 'nogcout'} {name} max-abs err: "
               f"split {err_s:.3e} fused {err_f:.3e}")
         assert torch.isfinite(f).all()
-        # Outside the envelope both runs are the same untiled kernels, whose
-        # weight gradient sums with float atomics: its error differs from
-        # run to run by more than 2x, so the ratio rule (a rule about the
-        # fused kernel's summation order) is applied where that kernel runs.
-        if fusable or name != "dweight":
-            assert err_f <= 2.0 * err_s, (name, err_f, err_s)
+        assert err_f <= 2.0 * err_s, (name, err_f, err_s)
         torch.testing.assert_close(f, r, atol=1e-3, rtol=1e-3)
-    if not fusable:
-        for name in ("ddata", "dconf"):  # the gathers repeat bit for bit
-            assert torch.equal(fused[name], split[name])
+    if W % 4:
+        # the unpadded planes themselves are outside every binding's envelope
+        import flowhip._C as C
+        u = {n: (v[..., :W].contiguous()
+                 if v is not None and v.dim() == 4 and n != "weight" else v)
+             for n, v in t.items()}
+        for algo in (-1, 0, 1):
+            with pytest.raises(RuntimeError):
+                _run(u, with_gcout, algo)
         with pytest.raises(RuntimeError):
-            _run(t, with_gcout, 1)
+            C.nconv_fwd(u["data"], u["conf"], u["weight"], u["bias"])
 
 
 @pytest.mark.parametrize("strip", [1, 2, 3])
@@ -194,6 +236,146 @@ def test_fused_is_deterministic(layer):
     b = _run(t, True, 1)
     for name in a:
         if a[name] is not None:
+            assert torch.equal(a[name], b[name]), name
+
+
+UNALIGNED_SIZES = [(7, 3), (5, 9), (18, 22), (6, 65)]
+UNALIGNED_LAYERS = [(1, 2, 5, False), (2, 2, 3, True), (2, 1, 1, False)]
+
+
+@pytest.mark.parametrize("use_cout", [True, False], ids=["out_cout", "out"])
+@pytest.mark.parametrize("layer", UNALIGNED_LAYERS,
+                         ids=["1to2_k5", "2to2_k3_bias", "2to1_k1"])
+@pytest.mark.parametrize("size", UNALIGNED_SIZES,
+                         ids=[f"{h}x{w}" for h, w in UNALIGNED_SIZES])
+def test_function_pads_unaligned_widths(size, layer, use_cout):
+    """NConv2dFn at W % 4 != 0 (W = 3 is narrower than one float4 chunk, 65
+    pads into a second tile column): outputs and gradients are, bit for bit,
+    the bindings' on the zero-padded planes, sliced; contiguous, of the
+    unpadded shape, and within the NConv cap of fp64."""
+    import flowhip._C as C
+    from flowhip.ops.functional_nconv import NConv2dFn
+    (H, W), (ci, co, k, has_bias) = size, layer
+    N, pad, dv = 2, -W % 4, _dev()
+    g = torch.Generator(device="cpu").manual_seed(9100 + 7 * H * W + 31 * ci + k)
+    data = torch.randn(N, ci, H, W, generator=g)
+    conf = 0.1 + 0.9 * torch.rand(N, ci, H, W, generator=g)
+    weight = torch.rand(co, ci, k, k, generator=g) + 0.05
+    bias = torch.randn(co, generator=g) if has_bias else None
+    gout = torch.randn(N, co, H, W, generator=g)
+    gcout = torch.randn(N, co, H, W, generator=g)
+    ref = _ref64(data, conf, weight, bias, gout, gcout, k)[use_cout]
+
+    leaves = [x.to(dv).requires_grad_(True) for x in (data, conf, weight)]
+    if has_bias:
+        leaves.append(bias.to(dv).requires_grad_(True))
+    out, cout = NConv2dFn.apply(leaves[0], leaves[1], leaves[2],
+                                leaves[3] if has_bias else None, k // 2, EPS,
+                                True)
+    outs, gs = [out], [gout.to(dv)]
+    if use_cout:
+        outs.append(cout)
+        gs.append(gcout.to(dv))
+    grads = torch.autograd.grad(outs, leaves, gs)
+    got = dict(out=out.detach(), cout=cout.detach(), ddata=grads[0],
+               dconf=grads[1], dweight=grads[2],
+               dbias=grads[3] if has_bias else None)
+
+    pd, pc = (_rpad(x, pad).to(dv) for x in (data, conf))
+    wd = weight.to(dv)
+    bd = bias.to(dv) if has_bias else None
+    pout, pcout = C.nconv_fwd(pd, pc, wd, bd)
+    r = C.nconv_bwd_fused(_rpad(gout, pad).to(dv),
+                          _rpad(gcout, pad).to(dv) if use_cout else None,
+                          pout, pcout, pd, pc, wd, bd, EPS, -1)
+    want = dict(out=pout[..., :W], cout=pcout[..., :W], ddata=r[0][..., :W],
+                dconf=r[1][..., :W], dweight=r[2],
+                dbias=r[3] if has_bias else None)
+    for name, w in want.items():
+        if w is None:
+            continue
+        assert got[name].shape == ref[name].shape, name
+        assert got[name].is_contiguous(), name
+        assert torch.equal(got[name], w), name
+        torch.testing.assert_close(got[name].double().cpu(), ref[name],
+                                   atol=1e-3, rtol=1e-3)
+
+
+def test_off_table_layer_takes_torch_path_with_warning():
+    """(Ci, Co, K) = (3, 2, 3) is in no kernel table (its weight gradient
+    used to abort): ops.nconv2d says so and runs torch_ref, forward and
+    backward."""
+    from flowhip import ops
+    from flowhip.ops import torch_ref
+    dv = _dev()
+    g = torch.Generator(device="cpu").manual_seed(9300)
+    data = torch.randn(2, 3, 12, 16, generator=g).to(dv).requires_grad_(True)
+    conf = (0.1 + 0.9 * torch.rand(2, 3, 12, 16, generator=g)).to(
+        dv).requires_grad_(True)
+    weight = (torch.rand(2, 3, 3, 3, generator=g) + 0.05).to(
+        dv).requires_grad_(True)
+    g1 = torch.randn(2, 2, 12, 16, generator=g).to(dv)
+    g2 = torch.randn(2, 2, 12, 16, generator=g).to(dv)
+    assert not ops.nconv2d_uses_hip(data, conf, weight, 1, 1, 1, 1, EPS, True)
+    # an in-table layer with the same arguments does, without a warning
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        assert ops.nconv2d_uses_hip(data[:, :2], conf[:, :2], weight[:, :2],
+                                    1, 1, 1, 1, EPS, True)
+    with pytest.warns(UserWarning, match=r"\(3, 2, 3\)"):
+        out, cout = ops.nconv2d(data, conf, weight, None, 1, 1, 1, 1, EPS,
+                                True)
+    grads = torch.autograd.grad((out, cout), (data, conf, weight), (g1, g2))
+    rl = [x.detach().clone().requires_grad_(True)
+          for x in (data, conf, weight)]
+    rout, rcout = torch_ref.nconv2d(rl[0], rl[1], rl[2], None, 1, 1, 1, 1,
+                                    EPS, True)
+    rgrads = torch.autograd.grad((rout, rcout), rl, (g1, g2))
+    torch.testing.assert_close(out, rout, atol=1e-4, rtol=1e-4)
+    torch.testing.assert_close(cout, rcout, atol=1e-4, rtol=1e-4)
+    for a, b in zip(grads, rgrads):
+        torch.testing.assert_close(a, b, atol=1e-3, rtol=1e-3)
+
+
+def test_split_env_var_runs_the_binding_algo0():
+    """FLOWHIP_NCONV_BWD=split makes NConv2dFn.backward run exactly
+    nconv_bwd_fused(algo=0), the split path the tests above measure: all
+    four gradients equal the binding's bit for bit. (The split path repeats
+    bit for bit: its plane sums add in a fixed order.)"""
+    from flowhip.ops.functional_nconv import NConv2dFn
+    case = (2, 2, 3, True, 19, 68, False)
+    t, _ = _case(case)
+    want = _run(t, True, 0)
+    leaves = [t[n].detach().clone().requires_grad_(True)
+              for n in ("data", "conf", "weight", "bias")]
+    out, cout = NConv2dFn.apply(leaves[0], leaves[1], leaves[2], leaves[3],
+                                1, EPS, True)
+    old = os.environ.get("FLOWHIP_NCONV_BWD")
+    os.environ["FLOWHIP_NCONV_BWD"] = "split"
+    try:
+        grads = torch.autograd.grad((out, cout), leaves,
+                                    (t["gout"], t["gcout"]))
+    finally:
+        if old is None:
+            del os.environ["FLOWHIP_NCONV_BWD"]
+        else:
+            os.environ["FLOWHIP_NCONV_BWD"] = old
+    names = ("ddata", "dconf", "dweight", "dbias")
+    for got, name in zip(grads, names):
+        d = (got.double() - want[name].double()).abs().max().item()
+        print(f"[nconv_bwd_split_env] {name} max-abs diff to algo=0: {d:.3e}")
+    for got, name in zip(grads, names):
+        assert torch.equal(got, want[name]), name
+
+
+def test_split_is_deterministic():
+    """algo=0 with bias and gcout, so that both plane sums run (dbias and
+    the sum(cout * gcout) term of dweight), ten block sums per channel."""
+    t, _ = _case((2, 2, 3, True, 37, 132, False))
+    a = _run(t, True, 0)
+    for _ in range(5):
+        b = _run(t, True, 0)
+        for name in a:
             assert torch.equal(a[name], b[name]), name
 
 

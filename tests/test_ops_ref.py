@@ -221,6 +221,7 @@ def test_extension_symbol_surface():
         "corr_pyramid_fwd", "corr_pyramid_bwd",
         "convex_up_fwd", "convex_up_bwd",
         "nconv_fwd", "nconv_bwd", "nconv_bwd_prep",
+        "nconv_bwd_fused", "nconv_supported",
         "conf_pool_fwd", "conf_pool_bwd",
         "zero_inject_fwd", "zero_inject_bwd",
         "gru_gate1_fwd", "gru_gate1_bwd", "gru_gate2_fwd", "gru_gate2_bwd",
