@@ -2,6 +2,7 @@
 
 #include <torch/extension.h>
 
+#include <cstdlib>
 #include <vector>
 
 #include <ATen/cuda/CUDAContext.h>
@@ -10,6 +11,7 @@
 
 // the conv family's geometry, plan and launchers
 #include "conv_gemm.h"
+#include "conv_fold.h"
 // the normalized-convolution family's
 #include "nconv.h"
 
@@ -1105,19 +1107,31 @@ static const void* cg_ptr(const c10::optional<torch::Tensor>& t) {
   return t.has_value() ? t->data_ptr() : nullptr;
 }
 
-torch::Tensor conv_gemm_pack(torch::Tensor w, bool flip) {
+// FLOWHIP_CONV_FOLD=0 keeps every conv off the tap-folded path (A/B
+// switch, default on): auto plans and the Python pack choice ask here.
+static bool conv_fold_enabled() {
+  const char* e = std::getenv("FLOWHIP_CONV_FOLD");
+  return !(e != nullptr && e[0] == '0' && e[1] == '\0');
+}
+
+// fold: the folded forward layout (KH, O, 64) of conv_fold.h
+torch::Tensor conv_gemm_pack(torch::Tensor w, bool flip, bool fold) {
   TORCH_CHECK(w.is_cuda() && w.is_contiguous() &&
               w.scalar_type() == torch::kFloat32 && w.dim() == 4);
   const int O = w.size(0), I = w.size(1), KH = w.size(2), KW = w.size(3);
+  TORCH_CHECK(!fold || (!flip && I <= 8 && KW <= 8),
+              "conv_gemm_pack: a folded pack is a forward pack of at most 8 "
+              "input channels and 8 taps per kernel row");
   const int R0 = flip ? I : O;
   const int cpad = cg_cpad(flip ? O : I);
-  auto wpk = torch::empty({(long)KH * KW, (long)R0, (long)cpad},
+  auto wpk = torch::empty({fold ? (long)KH : (long)KH * KW, (long)R0,
+                           (long)cpad},
                           w.options().dtype(torch::kBFloat16));
   const c10::cuda::CUDAGuard guard(w.device());
   hipStream_t stream = at::cuda::getCurrentCUDAStream().stream();
   flowhip_conv_gemm_pack_launch(w.data_ptr<float>(), wpk.data_ptr(),
                                 wpk.numel(), O, I, KH, KW, cpad,
-                                flip ? 1 : 0, stream);
+                                fold ? 2 : (flip ? 1 : 0), stream);
   return wpk;
 }
 
@@ -1125,10 +1139,10 @@ std::vector<torch::Tensor> conv_gemm_fwd2(
     torch::Tensor x, c10::optional<torch::Tensor> x2, torch::Tensor wpk,
     c10::optional<torch::Tensor> bias, int64_t Cout, int64_t KH, int64_t KW,
     int64_t osplit, int64_t act, int64_t sH, int64_t sW, int64_t smode,
-    int64_t outH, int64_t outW) {
+    int64_t outH, int64_t outW, bool fold) {
   TORCH_CHECK(wpk.is_cuda() && wpk.is_contiguous() &&
               wpk.scalar_type() == torch::kBFloat16 && wpk.dim() == 3);
-  TORCH_CHECK(wpk.size(0) == KH * KW && wpk.size(1) == Cout);
+  TORCH_CHECK(wpk.size(0) == (fold ? KH : KH * KW) && wpk.size(1) == Cout);
   TORCH_CHECK(smode >= 0 && smode <= 2 && sH >= 1 && sW >= 1);
   TORCH_CHECK(x.dim() == 4);
   // output spatial dims: same-pad for smode 0/1; smode 2 (strided
@@ -1148,6 +1162,12 @@ std::vector<torch::Tensor> conv_gemm_fwd2(
               "multiple of 64 channels");
   g.cpad = wpk.size(2);
   if (smode == 0) g.sH = g.sW = 1;  // smode 0 ignores the stride arguments
+  TORCH_CHECK(!fold || (smode <= 1 && wpk.size(2) == 64 &&
+                        (osplit <= 0 || osplit >= Cout) &&
+                        flowhip_conv_fold_envelope(g)),
+              "conv_gemm: a folded pack on a conv outside the folded "
+              "envelope (one source of 8 channels, KW <= 8, same padding, "
+              "stride 1 or 2, direct)");
   const float* bptr = nullptr;
   if (bias.has_value()) {
     TORCH_CHECK(bias->is_contiguous() &&
@@ -1163,7 +1183,7 @@ std::vector<torch::Tensor> conv_gemm_fwd2(
     flowhip_conv_gemm_fwd_launch(x.data_ptr(), cg_ptr(x2), wpk.data_ptr(),
                                  bptr, out.data_ptr(), nullptr,
                                  cg_zero_page(), g, (int)Cout, (int)act,
-                                 (int)smode, stream);
+                                 (int)smode, stream, fold);
     return {out};
   }
   TORCH_CHECK(smode == 0, "conv_gemm: osplit only with smode 0");
@@ -1182,7 +1202,7 @@ torch::Tensor conv_gemm_fwd(torch::Tensor x, torch::Tensor wpk,
                             c10::optional<torch::Tensor> bias, int64_t Cout,
                             int64_t KH, int64_t KW, int64_t act) {
   return conv_gemm_fwd2(x, c10::nullopt, wpk, bias, Cout, KH, KW, 0,
-                        act, 1, 1, 0, 0, 0)[0];
+                        act, 1, 1, 0, 0, 0, false)[0];
 }
 
 // Weight gradient. The one-shot conv_gemm_wrw is the three steps below in
@@ -1200,10 +1220,29 @@ static ConvGeom cg_wrw_geom(const torch::Tensor& dy, const torch::Tensor& x,
   return cg_geom(x, x2, dy.size(1), dy.size(2), dy.size(3), KH, KW, sH, sW);
 }
 
-// path (generic per-tap | halo-staged) and its split-M chunk count
+// path (generic per-tap | halo-staged | folded) and its split-M chunk
+// count. The folded decision is taken here, before the plan of conv_gemm.h:
+// auto takes path 2 inside its envelope. *form: the folded kernel's ky form
+// (ky_form: -1 its rule, 0 | 1 forced), 0 on the other paths.
 static int cg_wrw_plan(const ConvGeom& g, int64_t algo, int64_t nchunk_req,
-                       int* nchunk) {
-  TORCH_CHECK(algo >= -1 && algo <= 1, "conv_gemm_wrw: algo must be -1, 0, 1");
+                       int64_t ky_form, int* nchunk, int* form) {
+  TORCH_CHECK(algo >= -1 && algo <= 2,
+              "conv_gemm_wrw: algo must be -1, 0, 1, 2");
+  TORCH_CHECK(ky_form >= -1 && ky_form <= 1,
+              "conv_gemm_wrw: ky_form must be -1, 0, 1");
+  *form = 0;
+  const bool in_fold = flowhip_conv_fold_wrw_envelope(g);
+  TORCH_CHECK(algo != 2 || in_fold,
+              "conv_gemm_wrw: algo=2 (folded) forced on a shape outside its "
+              "envelope (one source of 8 channels, KW <= 8, same padding, "
+              "stride 1 or 2, Cout % 8 == 0)");
+  if (algo == 2 || (algo == -1 && in_fold && conv_fold_enabled())) {
+    *form = flowhip_conv_fold_wrw_plan(g, (int)ky_form, (int)nchunk_req,
+                                       nchunk);
+    TORCH_CHECK(*form >= 0,
+                "conv_gemm_wrw: ky_form=1 needs KH <= ", CF_MAXKY);
+    return 2;
+  }
   const int path =
       flowhip_conv_gemm_wrw_plan(g, (int)algo, (int)nchunk_req, nchunk);
   TORCH_CHECK(path >= 0,
@@ -1216,19 +1255,32 @@ std::vector<torch::Tensor> conv_gemm_wrw(torch::Tensor dy, torch::Tensor x,
                                          c10::optional<torch::Tensor> x2,
                                          int64_t KH, int64_t KW, int64_t sH,
                                          int64_t sW, bool want_bias,
-                                         int64_t algo, int64_t nchunk_req) {
+                                         int64_t algo, int64_t nchunk_req,
+                                         int64_t ky_form) {
   const ConvGeom g = cg_wrw_geom(dy, x, x2, KH, KW, sH, sW);
-  int nchunk = 1;
-  const int path = cg_wrw_plan(g, algo, nchunk_req, &nchunk);
+  int nchunk = 1, form = 0;
+  const int path = cg_wrw_plan(g, algo, nchunk_req, ky_form, &nchunk, &form);
   // every slot the reduce reads is written by the partials launch, and
   // dw / dbias fully by the reduce: no zero-fill
   const auto f32 = x.options().dtype(torch::kFloat32);
-  auto partials = torch::empty({g.buffer_numel(nchunk, want_bias)}, f32);
+  auto partials = torch::empty(
+      {path == 2 ? cf_buffer_numel(g, nchunk, want_bias)
+                 : g.buffer_numel(nchunk, want_bias)}, f32);
   auto dw = torch::empty({(long)g.Cout, (long)g.Cin, KH, KW}, f32);
   torch::Tensor dbias;
   if (want_bias) dbias = torch::empty({(long)g.Cout}, f32);
   const c10::cuda::CUDAGuard guard(x.device());
   hipStream_t stream = at::cuda::getCurrentCUDAStream().stream();
+  if (path == 2) {
+    flowhip_conv_fold_wrw_partials_launch(
+        dy.data_ptr(), x.data_ptr(), partials.data_ptr<float>(), want_bias,
+        cg_zero_page(), g, nchunk, form, false, stream);
+    flowhip_conv_fold_wrw_finish_launch(
+        partials.data_ptr<float>(), dw.data_ptr<float>(),
+        want_bias ? dbias.data_ptr<float>() : nullptr, g, nchunk, false,
+        stream);
+    return {dw, dbias};
+  }
   const bool launched = flowhip_conv_gemm_wrw_partials_launch(
       dy.data_ptr(), x.data_ptr(), cg_ptr(x2), partials.data_ptr<float>(),
       want_bias, cg_zero_page(), g, nchunk, path, false, stream);
@@ -1249,10 +1301,14 @@ std::vector<int64_t> conv_gemm_wrw_plan(torch::Tensor dy, torch::Tensor x,
                                         c10::optional<torch::Tensor> x2,
                                         int64_t KH, int64_t KW, int64_t sH,
                                         int64_t sW, bool want_bias,
-                                        int64_t algo, int64_t nchunk_req) {
+                                        int64_t algo, int64_t nchunk_req,
+                                        int64_t ky_form) {
   const ConvGeom g = cg_wrw_geom(dy, x, x2, KH, KW, sH, sW);
-  int nchunk = 1;
-  const int path = cg_wrw_plan(g, algo, nchunk_req, &nchunk);
+  int nchunk = 1, form = 0;
+  const int path = cg_wrw_plan(g, algo, nchunk_req, ky_form, &nchunk, &form);
+  if (path == 2)
+    return {path, nchunk, cf_buffer_numel(g, nchunk, want_bias),
+            flowhip_conv_fold_accumulate_wins() ? 1 : 0};
   return {path, nchunk, g.buffer_numel(nchunk, want_bias),
           flowhip_conv_gemm_wrw_accumulate_wins(path) ? 1 : 0};
 }
@@ -1264,23 +1320,33 @@ void conv_gemm_wrw_partials(torch::Tensor dy, torch::Tensor x,
                             c10::optional<torch::Tensor> x2,
                             torch::Tensor partials, int64_t KH, int64_t KW,
                             int64_t sH, int64_t sW, bool want_bias,
-                            bool accumulate, int64_t algo, int64_t nchunk) {
+                            bool accumulate, int64_t algo, int64_t nchunk,
+                            int64_t ky_form) {
   const ConvGeom g = cg_wrw_geom(dy, x, x2, KH, KW, sH, sW);
-  TORCH_CHECK(algo == 0 || algo == 1,
-              "conv_gemm_wrw_partials: algo must be a planned path (0 | 1)");
-  int planned = 0;
-  const int path =
-      flowhip_conv_gemm_wrw_plan(g, (int)algo, (int)nchunk, &planned);
-  TORCH_CHECK(path == algo && planned == nchunk && nchunk >= 1,
+  TORCH_CHECK(algo >= 0 && algo <= 2,
+              "conv_gemm_wrw_partials: algo must be a planned path (0 | 1 | "
+              "2)");
+  TORCH_CHECK(nchunk >= 1, "conv_gemm_wrw_partials: nchunk must be planned");
+  int planned = 0, form = 0;
+  const int path = cg_wrw_plan(g, algo, nchunk, ky_form, &planned, &form);
+  TORCH_CHECK(path == algo && planned == nchunk,
               "conv_gemm_wrw_partials: (algo, nchunk) is not a plan for "
               "these shapes");
   TORCH_CHECK(partials.is_cuda() && partials.is_contiguous() &&
               partials.scalar_type() == torch::kFloat32 &&
               partials.device() == x.device() &&
-              partials.numel() == g.buffer_numel((int)nchunk, want_bias),
+              partials.numel() ==
+                  (path == 2 ? cf_buffer_numel(g, (int)nchunk, want_bias)
+                             : g.buffer_numel((int)nchunk, want_bias)),
               "conv_gemm_wrw_partials: buffer does not match the plan");
   const c10::cuda::CUDAGuard guard(x.device());
   hipStream_t stream = at::cuda::getCurrentCUDAStream().stream();
+  if (path == 2) {
+    flowhip_conv_fold_wrw_partials_launch(
+        dy.data_ptr(), x.data_ptr(), partials.data_ptr<float>(), want_bias,
+        cg_zero_page(), g, (int)nchunk, form, accumulate, stream);
+    return;
+  }
   const bool launched = flowhip_conv_gemm_wrw_partials_launch(
       dy.data_ptr(), x.data_ptr(), cg_ptr(x2), partials.data_ptr<float>(),
       want_bias, cg_zero_page(), g, (int)nchunk, (int)algo, accumulate,
@@ -1296,14 +1362,21 @@ std::vector<torch::Tensor> conv_gemm_wrw_finish(
     torch::Tensor partials, int64_t Cout, int64_t Cin, int64_t KH,
     int64_t KW, bool want_bias, int64_t nchunk,
     c10::optional<torch::Tensor> dw_into,
-    c10::optional<torch::Tensor> dbias_into) {
+    c10::optional<torch::Tensor> dbias_into, int64_t path) {
   TORCH_CHECK(Cout >= 1 && Cin >= 1 && KH >= 1 && KW >= 1 && nchunk >= 1);
+  TORCH_CHECK(path >= 0 && path <= 2, "conv_gemm_wrw_finish: path 0 | 1 | 2");
+  const bool fold = path == 2;  // the folded buffer layout (conv_fold.h)
+  TORCH_CHECK(!fold || (Cin == 8 && KW <= 8),
+              "conv_gemm_wrw_finish: path 2 is the folded layout (Cin 8, "
+              "KW <= 8)");
   ConvGeom g{};  // the reduce needs the buffer layout only
   g.Cout = (int)Cout; g.Cin = (int)Cin; g.cpad = cg_cpad(g.Cin);
   g.KH = (int)KH; g.KW = (int)KW;
   TORCH_CHECK(partials.is_cuda() && partials.is_contiguous() &&
               partials.scalar_type() == torch::kFloat32 &&
-              partials.numel() == g.buffer_numel((int)nchunk, want_bias),
+              partials.numel() ==
+                  (fold ? cf_buffer_numel(g, (int)nchunk, want_bias)
+                        : g.buffer_numel((int)nchunk, want_bias)),
               "conv_gemm_wrw_finish: buffer does not match the shapes");
   const bool accumulate = dw_into.has_value();
   TORCH_CHECK(dbias_into.has_value() == (accumulate && want_bias),
@@ -1329,7 +1402,8 @@ std::vector<torch::Tensor> conv_gemm_wrw_finish(
   }
   const c10::cuda::CUDAGuard guard(partials.device());
   hipStream_t stream = at::cuda::getCurrentCUDAStream().stream();
-  flowhip_conv_gemm_wrw_finish_launch(
+  (fold ? flowhip_conv_fold_wrw_finish_launch
+        : flowhip_conv_gemm_wrw_finish_launch)(
       partials.data_ptr<float>(), dw.data_ptr<float>(),
       want_bias ? dbias.data_ptr<float>() : nullptr, g, (int)nchunk,
       accumulate, stream);
@@ -1719,7 +1793,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("transpose_cast_bf16", &transpose_cast_bf16,
         "(B,M,N) fp32 -> (B,N,M) bf16 tiled transpose");
   m.def("conv_gemm_pack", &conv_gemm_pack,
-        "one-kernel conv weight packing (fwd or flipped-bwd layout)");
+        "one-kernel conv weight packing (fwd, flipped-bwd or folded fwd "
+        "layout)",
+        py::arg("w"), py::arg("flip"), py::arg("fold") = false);
+  m.def("conv_fold_enabled", &conv_fold_enabled,
+        "false with FLOWHIP_CONV_FOLD=0: no conv takes the folded path "
+        "unless forced");
   m.def("conv_gemm_fwd", &conv_gemm_fwd,
         "implicit-GEMM NHWC bf16 conv forward (also bwd-data with flipped "
         "packed weights)");
@@ -1730,35 +1809,39 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("x"), py::arg("x2"), py::arg("wpk"), py::arg("bias"),
         py::arg("Cout"), py::arg("KH"), py::arg("KW"), py::arg("osplit"),
         py::arg("act"), py::arg("sH") = 1, py::arg("sW") = 1,
-        py::arg("smode") = 0, py::arg("outH") = 0, py::arg("outW") = 0);
+        py::arg("smode") = 0, py::arg("outH") = 0, py::arg("outW") = 0,
+        py::arg("fold") = false);
   m.def("conv_gemm_wrw", &conv_gemm_wrw,
         "implicit-GEMM conv weight gradient (split-M + reduce); returns "
         "[dw, dbias] — dbias undefined unless want_bias. algo: -1 auto, "
-        "0 generic per-tap kernel, 1 halo-staged kernel; nchunk: 0 auto",
+        "0 generic per-tap kernel, 1 halo-staged kernel, 2 folded kernel "
+        "(ky_form: -1 its rule, 0 ky in the grid, 1 ky looped); nchunk: 0 "
+        "auto",
         py::arg("dy"), py::arg("x"), py::arg("x2"), py::arg("KH"),
         py::arg("KW"), py::arg("sH") = 1, py::arg("sW") = 1,
         py::arg("want_bias") = false, py::arg("algo") = -1,
-        py::arg("nchunk") = 0);
+        py::arg("nchunk") = 0, py::arg("ky_form") = -1);
   m.def("conv_gemm_wrw_plan", &conv_gemm_wrw_plan,
         "weight-gradient plan for these shapes: [path, nchunk, partials "
         "buffer elements, accumulate (1: sum shared calls in the buffer)]",
         py::arg("dy"), py::arg("x"), py::arg("x2"), py::arg("KH"),
         py::arg("KW"), py::arg("sH") = 1, py::arg("sW") = 1,
         py::arg("want_bias") = false, py::arg("algo") = -1,
-        py::arg("nchunk") = 0);
+        py::arg("nchunk") = 0, py::arg("ky_form") = -1);
   m.def("conv_gemm_wrw_partials", &conv_gemm_wrw_partials,
         "one split-M partials launch into a caller-supplied buffer, no "
         "reduce; accumulate adds to the buffer instead of overwriting it",
         py::arg("dy"), py::arg("x"), py::arg("x2"), py::arg("partials"),
         py::arg("KH"), py::arg("KW"), py::arg("sH"), py::arg("sW"),
         py::arg("want_bias"), py::arg("accumulate"), py::arg("algo"),
-        py::arg("nchunk"));
+        py::arg("nchunk"), py::arg("ky_form") = -1);
   m.def("conv_gemm_wrw_finish", &conv_gemm_wrw_finish,
         "reduce a partials buffer over its chunks; returns [dw, dbias], "
         "added in place to dw_into / dbias_into when given",
         py::arg("partials"), py::arg("Cout"), py::arg("Cin"), py::arg("KH"),
         py::arg("KW"), py::arg("want_bias"), py::arg("nchunk"),
-        py::arg("dw_into") = py::none(), py::arg("dbias_into") = py::none());
+        py::arg("dw_into") = py::none(), py::arg("dbias_into") = py::none(),
+        py::arg("path") = 0);
   m.def("instnorm_cl_fwd", &instnorm_cl_fwd,
         "channels-last InstanceNorm2d forward (y, mean, rstd)");
   m.def("instnorm_cl_bwd", &instnorm_cl_bwd,

@@ -145,11 +145,14 @@ inline bool flowhip_conv_gemm_wrw_accumulate_wins(int path) {
 
 // conv_gemm.hip. smode: 0 stride-1 same padding, 1 strided direct, 2
 // strided transposed (see the file's header). out2 / osplit: split output.
+// fold: wpk is a folded pack and g is inside flowhip_conv_fold_envelope
+// (conv_fold.h), which the caller checked.
 void flowhip_conv_gemm_fwd_launch(const void* x, const void* x2,
                                   const void* wpk, const float* bias,
                                   void* out, void* out2, const void* zpage,
                                   const ConvGeom& g, int osplit, int act,
-                                  int smode, hipStream_t stream);
+                                  int smode, hipStream_t stream,
+                                  bool fold = false);
 // conv_halo.hip. Returns false (nothing launched) outside its envelope or
 // below its fill rule: the generic kernel takes the call.
 bool flowhip_conv_halo_fwd_launch(const void* x, const void* x2,

@@ -36,6 +36,11 @@
 //              conv_wrw_halo.hip (stride-1 same-padding 3x3 / 1x5 / 5x1),
 //              which stages dy and one x halo tile once for all taps.
 //              flowhip_conv_gemm_wrw_plan (conv_gemm.h) picks the path.
+//   folded:    convs of 8 input channels (the 7x7 encoder stems and convf1,
+//              zero-padded from 3 and 2) put the KW taps of a kernel row
+//              into one k-row and walk K over ky only: the FOLD variant of
+//              the forward kernel, conv_wrw_fold_kernel and its reduce.
+//              Envelope, plan and index maps: conv_fold.h.
 //
 // Host side: the launchers at the end of this file take a ConvGeom
 // (conv_gemm.h), which also holds the plan and every launcher's prototype.
@@ -47,6 +52,7 @@
 
 #include "common.h"
 #include "conv_gemm.h"
+#include "conv_fold.h"
 
 #define CG_BM 64
 #define CG_BN 64
@@ -83,13 +89,16 @@ __device__ __forceinline__ void cg_coords(
   }
 }
 
-template <int BM, int THREADS, int SMODE>
+// FOLD (conv_fold.h): the input has 8 channels, one pixel per piece; slot s
+// of a row holds tap kx = s of kernel row dy, i.e. pixel (sy, sx + s), and
+// slots >= KWf read the zero page. The bounds test is per piece.
+template <int BM, int THREADS, int SMODE, int FOLD>
 __device__ __forceinline__ void cg_stage_a(
     const __bf16* __restrict__ x, const __bf16* __restrict__ x2,
     const __bf16* __restrict__ zpage,
     char* lds_buf, int wave, int lane, const long* pn, const int* pyy,
     const int* pxx, int srcH, int srcW, int sH, int sW, int ld_x, int ld_x2,
-    int C1, int Cin, int dy, int dx, int c0) {
+    int C1, int Cin, int dy, int dx, int c0, int KWf) {
   constexpr int PPT = BM * 8 / THREADS;
 #pragma unroll
   for (int j = 0; j < PPT; ++j) {
@@ -103,11 +112,12 @@ __device__ __forceinline__ void cg_stage_a(
     const long n = pn[j];
     int sy, sx;
     bool ok;
+    const int fx = FOLD ? sslot : 0;
     if (SMODE == 0) {
-      sy = yy + dy; sx = xx + dx;
+      sy = yy + dy; sx = xx + dx + fx;
       ok = sy >= 0 && sy < srcH && sx >= 0 && sx < srcW;
     } else if (SMODE == 1) {
-      sy = yy * sH + dy; sx = xx * sW + dx;
+      sy = yy * sH + dy; sx = xx * sW + dx + fx;
       ok = sy >= 0 && sy < srcH && sx >= 0 && sx < srcW;
     } else {
       const int ty = yy + dy, tx = xx + dx;
@@ -115,10 +125,11 @@ __device__ __forceinline__ void cg_stage_a(
       ok = ty >= 0 && tx >= 0 && ty % sH == 0 && tx % sW == 0 &&
            sy < srcH && sx < srcW;
     }
-    const int c = c0 + sslot * 8;
+    const int c = FOLD ? 0 : c0 + sslot * 8;
+    if (FOLD) ok = ok && sslot < KWf;
     const __bf16* src = zpage;
     if (ok && c < Cin) {
-      if (x2 == nullptr || c < C1)
+      if (FOLD || x2 == nullptr || c < C1)
         src = x + (((long)n * srcH + sy) * srcW + sx) * ld_x + c;
       else
         src = x2 + (((long)n * srcH + sy) * srcW + sx) * ld_x2 + (c - C1);
@@ -157,8 +168,9 @@ __device__ __forceinline__ void cg_stage_b(const __bf16* __restrict__ wsec,
 }
 
 // ACT: 0 = none, 1 = ReLU. BM in {64, 128}: 64 -> 4 waves in a 2Mx2N
-// quadrant grid, 128 -> 8 waves as 4Mx2N.
-template <int ACT, int BM, int SMODE>
+// quadrant grid, 128 -> 8 waves as 4Mx2N. FOLD: K walks the KH kernel rows
+// of a folded pack (KH, Cout, 64), one k-step each (conv_fold.h).
+template <int ACT, int BM, int SMODE, int FOLD>
 __global__
 __launch_bounds__(BM == 64 ? 256 : 512, BM == 64 ? 2 : 4)
 void conv_gemm_fwd_kernel(
@@ -196,17 +208,17 @@ void conv_gemm_fwd_kernel(
 #pragma unroll
     for (int j = 0; j < 2; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
 
-  const int cslabs = cpad / CG_BK;
-  const int nsub = KH * KW * cslabs;
+  const int cslabs = FOLD ? 1 : cpad / CG_BK;
+  const int nsub = FOLD ? KH : KH * KW * cslabs;
 
   long pn[BM * 8 / THREADS];
   int pyy[BM * 8 / THREADS], pxx[BM * 8 / THREADS];
   cg_coords<BM, THREADS>(wave, lane, m0, Mtot, HH, WW, pn, pyy, pxx);
 
-  // subtile s -> (kyx = s / cslabs, c0 = (s % cslabs) * 64)
-  cg_stage_a<BM, THREADS, SMODE>(x, x2, zpage, lds, wave, lane, pn, pyy,
-                                 pxx, srcH, srcW, sH, sW, ld_x, ld_x2, C1,
-                                 Cin, offH, offW, 0);
+  // subtile s -> (kyx = s / cslabs, c0 = (s % cslabs) * 64); FOLD: s = ky
+  cg_stage_a<BM, THREADS, SMODE, FOLD>(x, x2, zpage, lds, wave, lane, pn,
+                                       pyy, pxx, srcH, srcW, sH, sW, ld_x,
+                                       ld_x2, C1, Cin, offH, offW, 0, KW);
   cg_stage_b<THREADS>(wpk, lds + TSA, wave, lane, n0, Cout, cpad, 0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -216,11 +228,12 @@ void conv_gemm_fwd_kernel(
     if (s + 1 < nsub) {
       const int kyx = (s + 1) / cslabs;
       const int cs = (s + 1) - kyx * cslabs;
-      const int ky = kyx / KW, kx = kyx - ky * KW;
-      cg_stage_a<BM, THREADS, SMODE>(
+      const int ky = FOLD ? kyx : kyx / KW;
+      const int kx = FOLD ? 0 : kyx - ky * KW;
+      cg_stage_a<BM, THREADS, SMODE, FOLD>(
           x, x2, zpage, lds + (cur ^ 1) * (TSA + TSB), wave, lane, pn, pyy,
           pxx, srcH, srcW, sH, sW, ld_x, ld_x2, C1, Cin, ky + offH,
-          kx + offW, cs * CG_BK);
+          kx + offW, cs * CG_BK, KW);
       cg_stage_b<THREADS>(wpk + (long)kyx * Cout * cpad,
                           lds + (cur ^ 1) * (TSA + TSB) + TSA, wave, lane,
                           n0, Cout, cpad, cs * CG_BK);
@@ -634,13 +647,313 @@ __global__ __launch_bounds__(CG_THREADS) void conv_gemm_wrw_reduce_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// Folded weight gradient (conv_fold.h): 8 input channels, the x tile's 64
+// columns are (kx, c8) of ONE kernel row, dWp[ky][o][kx*8+c] partial over
+// an M chunk. Same fragment scheme, same wrw_row_to_m image and the same
+// partials contract as conv_gemm_wrw_kernel above; the x staging piece of
+// column block cb, half ch is tap kx = cb*2 + ch, i.e. pixel (sy, sx + kx).
+//   NKY == 1:        ky = blockIdx.y, grid (tiles_o, KH, nchunk)
+//   NKY == CF_MAXKY: ky looped here, grid (tiles_o, 1, nchunk): a dy tile is
+//                    staged once and contracted against the KH x tiles that
+//                    stream through the x double buffer, into KH
+//                    accumulator sets (the ky loop is unrolled so the sets
+//                    stay in registers).
+// The k-steps of both forms are the flat sequence (m-tile, ky); step s
+// prefetches the x tile of step s+1 into the other x buffer and, when
+// that step opens a new m-tile, its dy tile into the other dy buffer (last
+// read during the previous m-tile, whose steps all ended in a barrier).
+// partials layout: (nchunk, KH, tiles_o*64, 64) fp32 + the bias tail.
+// ---------------------------------------------------------------------------
+template <int NKY>
+__global__ __launch_bounds__(CG_THREADS, 2) void conv_wrw_fold_kernel(
+    const __bf16* __restrict__ dy,  // (Mtot, Cout)
+    const __bf16* __restrict__ x,   // (N, srcH, srcW, ld_x), 8 channels
+    float* __restrict__ partials,
+    float* __restrict__ biasp,  // (nchunk, tiles_o*64) or nullptr
+    const __bf16* __restrict__ zpage,
+    long Mtot, int HH, int WW, int srcH, int srcW, int sH, int sW, int ld_x,
+    int Cout, int KH, int KW, int padH, int padW, int tiles_o, int nchunk,
+    int accumulate) {
+  constexpr unsigned TS = CG_BM * CG_BK * 2;
+  // [dy 0][dy 1][x 0][x 1]
+  __shared__ __attribute__((aligned(16))) char lds[4 * TS];
+
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6;
+  const int lane = tid & 63;
+
+  const int to = blockIdx.x;
+  const int form = NKY == 1 ? 0 : 1;
+  const int ky0 = cf_ky0(form, blockIdx.y);
+  const int nky = cf_nky(form, KH);
+  const int chunk = blockIdx.z;
+  const int o0 = to * 64;
+
+  const long mtiles = (Mtot + CG_BM - 1) / CG_BM;
+  const long t0 = (mtiles * chunk) / nchunk;
+  const long t1 = (mtiles * (chunk + 1)) / nchunk;
+
+  const int wr = (wave >> 1) * 32;  // o offset
+  const int wc = (wave & 1) * 32;   // (kx, c) column offset
+
+  f32x4 acc[NKY][2][2];
+#pragma unroll
+  for (int k = 0; k < NKY; ++k)
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) acc[k][i][j] = {0.f, 0.f, 0.f, 0.f};
+
+  // bias gradient as in conv_gemm_wrw_kernel: the even waves of the ky == 0
+  // step hold every dy fragment exactly once
+  const bool bias_waves = biasp != nullptr && wc == 0;
+  float bacc[2] = {0.f, 0.f};
+
+  // this thread's two staging pieces: image row -> tile m, column start
+  int p_dm[2], p_col[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int piece = wave * 64 + CG_THREADS * j + lane;
+    const int sb = piece >> 3;
+    const int pr = (piece >> 1) & 3;
+    const int ch = piece & 1;
+    p_dm[j] = wrw_row_to_m((sb & 15) * 4 + pr);
+    p_col[j] = (sb >> 4) * 16 + ch * 8;  // dy: o offset; x: kx * 8
+  }
+
+  auto stage_dy = [&](long mt, char* buf) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int piece0 = wave * 64 + CG_THREADS * j;
+      const long m = mt * CG_BM + p_dm[j];
+      const int o = o0 + p_col[j];
+      const __bf16* src = (m < Mtot && o < Cout) ? dy + m * Cout + o : zpage;
+      __builtin_amdgcn_global_load_lds(
+          (const __attribute__((address_space(1))) void*)src,
+          (__attribute__((address_space(3))) void*)(buf + piece0 * 16),
+          16, 0, 0);
+    }
+  };
+  // coordinates of the first pixel of the m-tile being staged
+  long base_m = t0 * CG_BM;
+  int bx = 0, by = 0;
+  long bn = 0;
+  if (t0 < t1) {
+    bx = (int)(base_m % WW);
+    by = (int)((base_m / WW) % HH);
+    bn = base_m / ((long)WW * HH);
+  }
+  auto advance_base = [&]() {
+    base_m += CG_BM;
+    bx += CG_BM;
+    while (bx >= WW) {
+      bx -= WW;
+      if (++by == HH) { by = 0; ++bn; }
+    }
+  };
+  auto stage_x = [&](int ky, char* buf) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int piece0 = wave * 64 + CG_THREADS * j;
+      const int dm = p_dm[j];
+      const int kx = p_col[j] >> 3;
+      const __bf16* src = zpage;
+      if (base_m + dm < Mtot && kx < KW) {
+        int xx = bx + dm, yy = by;
+        long n = bn;
+        while (xx >= WW) {
+          xx -= WW;
+          if (++yy == HH) { yy = 0; ++n; }
+        }
+        const int sy = yy * sH + ky - padH, sx = xx * sW + kx - padW;
+        if (sy >= 0 && sy < srcH && sx >= 0 && sx < srcW)
+          src = x + (((long)n * srcH + sy) * srcW + sx) * ld_x;
+      }
+      __builtin_amdgcn_global_load_lds(
+          (const __attribute__((address_space(1))) void*)src,
+          (__attribute__((address_space(3))) void*)(buf + piece0 * 16),
+          16, 0, 0);
+    }
+  };
+
+  char* const dyb = lds;
+  char* const xb = lds + 2 * TS;
+  if (t0 < t1) {
+    stage_dy(t0, dyb);
+    stage_x(ky0, xb);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+
+  int xcur = 0, dcur = 0;
+  const unsigned lb = (unsigned)lane * 8;
+  for (long t = t0; t < t1; ++t) {
+#pragma unroll
+    for (int k = 0; k < NKY; ++k) {
+      if (k < nky) {
+        if (k + 1 < nky) {
+          stage_x(ky0 + k + 1, xb + (xcur ^ 1) * TS);
+        } else if (t + 1 < t1) {
+          advance_base();
+          stage_dy(t + 1, dyb + (dcur ^ 1) * TS);
+          stage_x(ky0, xb + (xcur ^ 1) * TS);
+        }
+
+        const char* dbuf = dyb + dcur * TS;
+        const char* xbuf = xb + xcur * TS;
+        const bool do_bias = bias_waves && ky0 + k == 0;
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) {
+          bf16x4 a0[2], a1[2], b0[2], b1[2];
+#pragma unroll
+          for (int i = 0; i < 2; ++i) {
+            const unsigned cb = (unsigned)(wr >> 4) + i;  // o column block
+            a0[i] = wrw_tr_read(dbuf, (cb * 16 + kk * 8 + 0) * 128 + lb);
+            a1[i] = wrw_tr_read(dbuf, (cb * 16 + kk * 8 + 4) * 128 + lb);
+          }
+#pragma unroll
+          for (int j = 0; j < 2; ++j) {
+            const unsigned cb = (unsigned)(wc >> 4) + j;  // taps 2cb, 2cb+1
+            b0[j] = wrw_tr_read(xbuf, (cb * 16 + kk * 8 + 0) * 128 + lb);
+            b1[j] = wrw_tr_read(xbuf, (cb * 16 + kk * 8 + 4) * 128 + lb);
+          }
+          asm volatile("s_waitcnt lgkmcnt(0)"
+                       : "+v"(a0[0]), "+v"(a0[1]), "+v"(a1[0]), "+v"(a1[1]),
+                         "+v"(b0[0]), "+v"(b0[1]), "+v"(b1[0]), "+v"(b1[1])
+                       :: "memory");
+          __builtin_amdgcn_sched_barrier(0);
+
+#pragma unroll
+          for (int i = 0; i < 2; ++i) {
+            const bf16x8 af = __builtin_shufflevector(a0[i], a1[i], 0, 1, 2,
+                                                      3, 4, 5, 6, 7);
+            if (do_bias) {
+#pragma unroll
+              for (int e = 0; e < 8; ++e) bacc[i] += (float)af[e];
+            }
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+              const bf16x8 bf = __builtin_shufflevector(b0[j], b1[j], 0, 1,
+                                                        2, 3, 4, 5, 6, 7);
+              acc[k][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                  af, bf, acc[k][i][j], 0, 0, 0);
+            }
+          }
+        }
+
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        xcur ^= 1;
+      }
+    }
+    dcur ^= 1;
+  }
+
+  // one owning thread per slot (cf_acc_orow / cf_acc_col); accumulate adds
+  // in call order, a set's 16 loads issued before its stores
+  const int orows = tiles_o * 64;
+#pragma unroll
+  for (int k = 0; k < NKY; ++k) {
+    if (k < nky) {
+      float* pt = partials + cf_partial_index(chunk, ky0 + k, o0, 0, KH, orows);
+      if (accumulate) {
+        float prev[2][2][4];
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              prev[i][j][r] = pt[cf_acc_orow(wave, lane, i, r) * 64 +
+                                 cf_acc_col(wave, lane, j)];
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[k][i][j][r] += prev[i][j][r];
+      }
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            pt[cf_acc_orow(wave, lane, i, r) * 64 +
+               cf_acc_col(wave, lane, j)] = acc[k][i][j][r];
+    }
+  }
+
+  if (bias_waves && ky0 == 0) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      float s = bacc[i];
+      s += __shfl_xor(s, 16, 64);
+      s += __shfl_xor(s, 32, 64);
+      if (lane < 16) {
+        float* bp = biasp + cf_bias_index(
+                                chunk, o0 + cf_bias_orow(wave, lane, i), orows);
+        if (accumulate) s += *bp;
+        *bp = s;
+      }
+    }
+  }
+}
+
+// reduce the folded partials over chunks (ascending) into dW (Cout, Cin,
+// KH, KW): consecutive threads take consecutive (kx, c) columns of one
+// (ky, o) row, so every chunk's read is one contiguous run of KW * 8 floats.
+// The ky-looped form fills the chip with ~256 chunks where the generic
+// path has about ten; a plain running sum over that many terms measured 4x
+// the generic path's dbias error at 2x161x161, so the chunk sums are
+// compensated (Kahan; the build has no fast-math to undo it). Still one
+// ascending pass, bit-reproducible, and free in a memory-bound kernel.
+__device__ __forceinline__ void cf_kahan_add(float& s, float& comp, float v) {
+  const float y = v - comp;
+  const float t = s + y;
+  comp = (t - s) - y;
+  s = t;
+}
+
+__global__ __launch_bounds__(CG_THREADS) void conv_wrw_fold_reduce_kernel(
+    const float* __restrict__ partials, float* __restrict__ dw,
+    const float* __restrict__ biasp, float* __restrict__ dbias, int nchunk,
+    int KH, int KW, int orows, int Cout, int Cin, int accumulate) {
+  if (dbias)
+    for (int o = blockIdx.x * CG_THREADS + threadIdx.x; o < Cout;
+         o += gridDim.x * CG_THREADS) {
+      float s = 0.f, comp = 0.f;
+      for (int ch = 0; ch < nchunk; ++ch)
+        cf_kahan_add(s, comp, biasp[cf_bias_index(ch, o, orows)]);
+      dbias[o] = accumulate ? dbias[o] + s : s;
+    }
+  const int cols = KW * 8;
+  const long total = (long)KH * Cout * cols;
+  for (long idx = (long)blockIdx.x * CG_THREADS + threadIdx.x; idx < total;
+       idx += (long)gridDim.x * CG_THREADS) {
+    long t = idx;
+    const int col = (int)(t % cols); t /= cols;
+    const int o = (int)(t % Cout); t /= Cout;
+    const int ky = (int)t;
+    const int kx = col >> 3, c = col & 7;
+    if (c >= Cin) continue;
+    float s = 0.f, comp = 0.f;
+    for (int ch = 0; ch < nchunk; ++ch)
+      cf_kahan_add(s, comp,
+                   partials[cf_partial_index(ch, ky, o, col, KH, orows)]);
+    float* d = dw + cf_dw_index(o, c, ky, kx, Cin, KH, KW);
+    *d = accumulate ? *d + s : s;
+  }
+}
+
+// ---------------------------------------------------------------------------
 
 template <int BM>
 static void cg_fwd_dispatch(const __bf16* x, const __bf16* x2,
                             const __bf16* wpk, const float* bias, __bf16* out,
                             __bf16* out2, const __bf16* zpage,
                             const ConvGeom& g, int osplit, int act, int smode,
-                            hipStream_t stream) {
+                            bool fold, hipStream_t stream) {
   // tap offsets: direct conv (smode 0/1) reads sy = oy*sH + ky - padH;
   // strided-transposed (smode 2) taps t = iy + ky + (padH - KH + 1)
   const int offH = smode == 2 ? g.padH - g.KH + 1 : -g.padH;
@@ -648,15 +961,22 @@ static void cg_fwd_dispatch(const __bf16* x, const __bf16* x2,
   const int tiles_m = (int)((g.Mtot + BM - 1) / BM);
   const int tiles_n = fh_cdiv(g.Cout, CG_BN);
   dim3 grid(tiles_m * tiles_n), block(BM == 64 ? 256 : 512);
-#define CG_LAUNCH(A, S)                                                      \
-  hipLaunchKernelGGL((conv_gemm_fwd_kernel<A, BM, S>), grid, block, 0,       \
+#define CG_LAUNCH(A, S, F)                                                   \
+  hipLaunchKernelGGL((conv_gemm_fwd_kernel<A, BM, S, F>), grid, block, 0,    \
                      stream, x, x2, wpk, bias, out, out2, zpage, g.Mtot,     \
                      g.HH, g.WW, g.srcH, g.srcW, g.sH, g.sW, g.ld_x,         \
                      g.ld_x2, g.C1, g.Cin, g.Cout, g.cpad, g.KH, g.KW, offH, \
                      offW, osplit, tiles_m)
-  if (smode == 0) { if (act == 1) CG_LAUNCH(1, 0); else CG_LAUNCH(0, 0); }
-  else if (smode == 1) { if (act == 1) CG_LAUNCH(1, 1); else CG_LAUNCH(0, 1); }
-  else { if (act == 1) CG_LAUNCH(1, 2); else CG_LAUNCH(0, 2); }
+  if (fold) {  // smode 0 | 1 only (flowhip_conv_fold_envelope)
+    if (smode == 0) {
+      if (act == 1) CG_LAUNCH(1, 0, 1); else CG_LAUNCH(0, 0, 1);
+    } else {
+      if (act == 1) CG_LAUNCH(1, 1, 1); else CG_LAUNCH(0, 1, 1);
+    }
+  }
+  else if (smode == 0) { if (act == 1) CG_LAUNCH(1, 0, 0); else CG_LAUNCH(0, 0, 0); }
+  else if (smode == 1) { if (act == 1) CG_LAUNCH(1, 1, 0); else CG_LAUNCH(0, 1, 0); }
+  else { if (act == 1) CG_LAUNCH(1, 2, 0); else CG_LAUNCH(0, 2, 0); }
 #undef CG_LAUNCH
 }
 
@@ -664,11 +984,12 @@ void flowhip_conv_gemm_fwd_launch(const void* x, const void* x2,
                                   const void* wpk, const float* bias,
                                   void* out, void* out2, const void* zpage,
                                   const ConvGeom& g, int osplit, int act,
-                                  int smode, hipStream_t stream) {
+                                  int smode, hipStream_t stream, bool fold) {
   // stride-1 3x3 / 1x5 / 5x1 (the dominant shapes incl. their
   // backward-data): the halo-staged kernel stages the input once for all
   // KH*KW taps
-  if (smode == 0 && out2 == nullptr &&
+  // (a folded pack has another layout: the bindings checked the envelope)
+  if (!fold && smode == 0 && out2 == nullptr &&
       flowhip_conv_halo_fwd_launch(x, x2, wpk, bias, out, zpage, g, act,
                                    stream))
     return;
@@ -680,11 +1001,12 @@ void flowhip_conv_gemm_fwd_launch(const void* x, const void* x2,
     cg_fwd_dispatch<128>((const __bf16*)x, (const __bf16*)x2,
                          (const __bf16*)wpk, bias, (__bf16*)out,
                          (__bf16*)out2, (const __bf16*)zpage, g, osplit, act,
-                         smode, stream);
+                         smode, fold, stream);
   else
     cg_fwd_dispatch<64>((const __bf16*)x, (const __bf16*)x2,
                         (const __bf16*)wpk, bias, (__bf16*)out, (__bf16*)out2,
-                        (const __bf16*)zpage, g, osplit, act, smode, stream);
+                        (const __bf16*)zpage, g, osplit, act, smode, fold,
+                        stream);
 }
 
 // The weight gradient runs in two steps that share one partials buffer;
@@ -743,12 +1065,48 @@ void flowhip_conv_gemm_wrw_finish_launch(const float* partials, float* dw,
                      g.Cin, accumulate ? 1 : 0);
 }
 
+// The folded pair (conv_fold.h): same two steps, same buffer contract, the
+// folded partials layout. form / nchunk from flowhip_conv_fold_wrw_plan.
+void flowhip_conv_fold_wrw_partials_launch(const void* dy, const void* x,
+                                           float* partials, bool want_bias,
+                                           const void* zpage,
+                                           const ConvGeom& g, int nchunk,
+                                           int form, bool accumulate,
+                                           hipStream_t stream) {
+  float* biasp = want_bias ? partials + cf_wpartials_numel(g, nchunk) : nullptr;
+  dim3 grid(g.tiles_o(), cf_grid_y(g, form), nchunk), block(CG_THREADS);
+#define CF_LAUNCH(NKY)                                                       \
+  hipLaunchKernelGGL(conv_wrw_fold_kernel<NKY>, grid, block, 0, stream,      \
+                     (const __bf16*)dy, (const __bf16*)x, partials, biasp,   \
+                     (const __bf16*)zpage, g.Mtot, g.HH, g.WW, g.srcH,       \
+                     g.srcW, g.sH, g.sW, g.ld_x, g.Cout, g.KH, g.KW, g.padH, \
+                     g.padW, g.tiles_o(), nchunk, accumulate ? 1 : 0)
+  if (form == 1) CF_LAUNCH(CF_MAXKY); else CF_LAUNCH(1);
+#undef CF_LAUNCH
+}
+
+void flowhip_conv_fold_wrw_finish_launch(const float* partials, float* dw,
+                                         float* dbias, const ConvGeom& g,
+                                         int nchunk, bool accumulate,
+                                         hipStream_t stream) {
+  const long total = (long)g.KH * g.Cout * g.KW * 8;
+  long rblocks = (total + CG_THREADS - 1) / CG_THREADS;
+  if (rblocks > 4096) rblocks = 4096;
+  hipLaunchKernelGGL(conv_wrw_fold_reduce_kernel, dim3((int)rblocks),
+                     dim3(CG_THREADS), 0, stream, partials, dw,
+                     dbias ? partials + cf_wpartials_numel(g, nchunk) : nullptr,
+                     dbias, nchunk, g.KH, g.KW, g.tiles_o() * 64, g.Cout,
+                     g.Cin, accumulate ? 1 : 0);
+}
+
 // ---------------------------------------------------------------------------
 // Weight packing (host-side cache refill after every optimizer step): one
 // gather kernel instead of the ~5-op torch chain (permute/reshape/pad/cast/
 // contiguous) per pack, ~52 packs per training step.
 //   fwd pack:  wpk[kyx][o][c]  = c < I ? w[o][c][ky][kx] : 0     (bf16)
 //   bwd pack:  wpk[kyx][i][oc] = oc < O ? w[oc][i][KH-1-ky][KW-1-kx] : 0
+//   folded (flip == 2, conv_fold.h):
+//              wpk[ky][o][kx*8+c] = kx < KW && c < I ? w[o][c][ky][kx] : 0
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void conv_gemm_pack_kernel(
     const float* __restrict__ w,  // (O, I, KH, KW)
@@ -759,10 +1117,15 @@ __global__ __launch_bounds__(256) void conv_gemm_pack_kernel(
        idx += (long)gridDim.x * 256) {
     long t = idx;
     const int c = t % cpad; t /= cpad;
-    const int r = t % (flip ? I : O); t /= (flip ? I : O);
+    const int r = t % (flip == 1 ? I : O); t /= (flip == 1 ? I : O);
     const int kyx = (int)t;
     float v = 0.f;
-    if (!flip) {
+    if (flip == 2) {
+      // folded: cpad == 64, r = o, t = ky, c = kx * 8 + channel
+      // (inverse of cf_pack_index)
+      const int kx = c >> 3, ci = c & 7;
+      if (kx < KW && ci < I) v = w[(((long)r * I + ci) * KYX) + kyx * KW + kx];
+    } else if (!flip) {
       if (c < I) v = w[(((long)r * I + c) * KYX) + kyx];
     } else {
       // r = input channel, c = output channel, spatially flipped

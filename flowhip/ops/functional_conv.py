@@ -11,6 +11,11 @@ cached per weight version so they are rebuilt only after optimizer steps.
   bwd-wrw:   dW  = split-M MFMA partials + reduce (fp32)
   bwd-bias:  per-chunk column sums from the same partials kernel
 
+Convs whose padded input has exactly 8 channels (the 7x7 encoder stems and
+convf1) take the tap-folded kernels of csrc/conv_fold.h: the forward through
+a folded pack chosen here (_fold_ok), the weight gradient through the
+extension's plan (path 2). FLOWHIP_CONV_FOLD=0 switches both off.
+
 Inside wrw_accumulate_scope() (the models open it around the refinement
 loop) a conv that is called K times with the same weights sums its K weight
 gradients natively and hands the parameter ONE gradient, from the backward
@@ -77,12 +82,31 @@ def _log_fallback(tag, x, describe):
         print(f"[{tag} fallback] {describe()}", flush=True)
 
 
-def _pack_fwd(weight):
-    """(O, I, KH, KW) fp32 -> (KYX, O, pad64(I)) bf16 contiguous."""
+def conv_fold_enabled():
+    """FLOWHIP_CONV_FOLD=0 keeps the small-Cin convs off the tap-folded
+    kernels (A/B switch; default on). The extension reads the variable, for
+    its auto weight-gradient plan and for the pack choice here."""
+    return _ext.ext().conv_fold_enabled()
+
+
+def _fold_ok(x, weight):
+    """The folded envelope (csrc/conv_fold.h) for a conv can_fuse_conv
+    accepted: 8 input channels in whole 16-byte pixels, KW <= 8."""
+    return (conv_fold_enabled() and weight.shape[1] == 8
+            and weight.shape[3] <= 8 and x.stride(3) % 8 == 0)
+
+
+def _pack_fwd(weight, fold=False):
+    """(O, I, KH, KW) fp32 -> (KYX, O, pad64(I)) bf16 contiguous; folded:
+    (KH, O, 64) with column kx * 8 + c."""
     w = weight.detach()
     if w.is_cuda and w.dtype == torch.float32:
-        return _ext.ext().conv_gemm_pack(w.contiguous(), False)
+        return _ext.ext().conv_gemm_pack(w.contiguous(), False, fold)
     O, I, KH, KW = w.shape
+    if fold:
+        w = w.to(torch.bfloat16).permute(2, 0, 3, 1)  # (KH, O, KW, I)
+        w = F.pad(w, (0, 8 - I, 0, 8 - KW))
+        return w.reshape(KH, O, 64).contiguous()
     w = w.to(torch.bfloat16).permute(2, 3, 0, 1).reshape(KH * KW, O, I)
     return F.pad(w, (0, _pad64(I) - I)).contiguous()
 
@@ -104,12 +128,13 @@ def _weight_key(*tensors):
     return tuple(v for t in tensors for v in (t.data_ptr(), t._version))
 
 
-def _packs(weight, cache, key=None):
+def _packs(weight, cache, key=None, fold=False):
     if key is None:
         key = _weight_key(weight)
-    if cache.get("k") != key:
+    if cache.get("k") != key or cache.get("fold", False) != fold:
         cache["k"] = key
-        cache["fwd"] = _pack_fwd(weight)
+        cache["fold"] = fold
+        cache["fwd"] = _pack_fwd(weight, fold)
         cache["bwd"] = _pack_bwd(weight)
     return cache["fwd"], cache["bwd"]
 
@@ -150,7 +175,8 @@ class _WrwHandle:
     def __init__(self):
         self.buf = None    # partials buffer, kept until the sink runs
         self.live = False  # buf holds the summed partials of earlier calls
-        self.plan = None   # (path, nchunk, numel, accumulate) buf is for
+        self.plan = None   # (path, nchunk, numel, accumulate) buf is for;
+        #                    path 2 (folded) has a buffer layout of its own
         self.geom = None   # (Cout padded to 8, Cin, KH, KW, has_bias)
         self.dw = None     # running sums of the calls already reduced,
         self.db = None     # over the padded Cout
@@ -200,7 +226,7 @@ def _finish_into_running(h):
     Op, Cin, KH, KW, has_bias = h.geom
     dw, db = _ext.ext().conv_gemm_wrw_finish(
         h.buf, Op, Cin, KH, KW, has_bias, h.plan[1], h.dw,
-        h.db if has_bias else None)
+        h.db if has_bias else None, h.plan[0])
     return dw, (db if has_bias else None)
 
 
@@ -276,16 +302,18 @@ class ConvGemmFn(torch.autograd.Function):
     the virtually-concatenated pair cat([x, x2], 1): no per-call cat
     materialization and no backward narrows (4 per GRU iteration); x's
     channel count must then be a multiple of 64. Stride 1, or strided
-    (smode 1 fwd / smode 2 bwd-data) with a single source."""
+    (smode 1 fwd / smode 2 bwd-data) with a single source. fold: wpk_fwd
+    is a folded pack (the forward only; the backward-data keeps the
+    generic pack and the weight gradient plans its own path)."""
 
     @staticmethod
     def forward(ctx, x, x2, weight, bias, wpk_fwd, wpk_bwd, sH, sW,
-                handle=None):
+                handle=None, fold=False):
         O, I, KH, KW = weight.shape
         b = bias.detach().float().contiguous() if bias is not None else None
         smode = 0 if (sH, sW) == (1, 1) else 1
         out = _ext.ext().conv_gemm_fwd2(x, x2, wpk_fwd, b, O, KH, KW, 0, 0,
-                                        sH, sW, smode)[0]
+                                        sH, sW, smode, 0, 0, fold)[0]
         ctx.save_for_backward(x, x2, wpk_bwd)
         ctx.meta = (I, KH, KW, bias is not None, sH, sW)
         ctx.handle = handle
@@ -309,7 +337,7 @@ class ConvGemmFn(torch.autograd.Function):
         if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
             dw, dbias = _wrw(ctx.handle, dyp, x, x2, KH, KW, sH, sW,
                              has_bias, O_real)
-        return dx, dx2, dw, dbias, None, None, None, None, None
+        return dx, dx2, dw, dbias, None, None, None, None, None, None
 
 
 def can_fuse_conv(x, weight, stride, padding, dilation, groups):
@@ -370,10 +398,11 @@ def fused_conv2d(x, weight, bias, stride, padding, dilation, groups, cache,
             weight = wh
         elif pad8:
             x, weight = _pad_c8(x, weight)
-        wf, wb = _packs(weight, cache, key)
+        fold = _fold_ok(x, weight)
+        wf, wb = _packs(weight, cache, key, fold)
         sH, sW = _pair(stride)
         return ConvGemmFn.apply(x, None, weight, bias, wf, wb, sH, sW,
-                                handle)
+                                handle, fold)
     _log_fallback("conv", x, lambda: (
         f"w={tuple(weight.shape)} stride={stride} "
         f"pad={padding} dil={dilation} g={groups} x={tuple(x.shape)} "

@@ -47,6 +47,9 @@ LOOP_EXTRA = [("upd_324to256_1x1", 3, 56, 128, 324, 0, 256, 1, 1, 4),
               ("upd_8to128_7x7", 3, 56, 128, 8, 0, 128, 7, 7, 0)]
 
 
+PATHS = {0: "generic", 1: "halo", 2: "folded"}
+
+
 def _cl(b, c, h, w, dev):
     t = (torch.randn(b, c, h, w, device=dev) / 4).to(torch.bfloat16)
     return t.contiguous(memory_format=torch.channels_last)
@@ -95,7 +98,7 @@ def accumulate_mode(args, C, dev):
                 C.conv_gemm_wrw_partials(dy, x1, x2, buf, KH, KW, 1, 1, True,
                                          i > 0, path, nchunk)
             return C.conv_gemm_wrw_finish(buf, op, C1 + C2, KH, KW, True,
-                                          nchunk)
+                                          nchunk, None, None, path)
 
         def finish_into():
             buf = torch.empty(numel, dtype=torch.float32, device=dev)
@@ -104,7 +107,7 @@ def accumulate_mode(args, C, dev):
                 C.conv_gemm_wrw_partials(dy, x1, x2, buf, KH, KW, 1, 1, True,
                                          False, path, nchunk)
                 dw, db = C.conv_gemm_wrw_finish(buf, op, C1 + C2, KH, KW,
-                                                True, nchunk, dw, db)
+                                                True, nchunk, dw, db, path)
             return dw, db
 
         dw_o, db_o = one_shot()
@@ -124,7 +127,7 @@ def accumulate_mode(args, C, dev):
         print(json.dumps({
             "shape": name, "B": B, "H": H, "W": W, "Cin": C1 + C2,
             "Cout": Cout, "K": f"{KH}x{KW}", "calls": args.calls,
-            "path": "halo" if path == 1 else "generic", "nchunk": nchunk,
+            "path": PATHS[path], "nchunk": nchunk,
             "partials_MB": round(numel * 4 / 2 ** 20, 2),
             "us_per_pass": {k: round(v, 1) for k, v in med.items()},
             "us_min": {k: round(min(v), 1) for k, v in times.items()},
