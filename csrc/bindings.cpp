@@ -49,8 +49,8 @@ void flowhip_convex_up_fwd_launch(const float* flow, const float* mask,
                                   hipStream_t stream);
 void flowhip_convex_up_bwd_launch(const float* gout, const float* flow,
                                   const float* mask, float* gflow,
-                                  float* gmask, int N, int H, int W,
-                                  int factor, hipStream_t stream);
+                                  float* gmask, float* contrib, int N, int H,
+                                  int W, int factor, hipStream_t stream);
 int flowhip_instnorm_partial_rows(int N, int C, long P);
 void flowhip_transpose_cast_launch(const void* in, void* out, int B, int M,
                                    int N, int in_bf16, hipStream_t stream);
@@ -66,12 +66,13 @@ void flowhip_conf_pool_bwd_launch(const float* gdata_ds,
 void flowhip_instnorm_cl_fwd_launch(const void* x, void* y, float* mean,
                                     float* rstd, float* partials, int N,
                                     int C, long P, float eps, int is_bf16,
-                                    hipStream_t stream);
+                                    bool deterministic, hipStream_t stream);
 void flowhip_instnorm_cl_bwd_launch(const void* x, const void* dy,
                                     const float* mean, const float* rstd,
                                     float* gmean, float* gxmean,
                                     float* partials, void* dx, int N, int C,
-                                    long P, int is_bf16, hipStream_t stream);
+                                    long P, int is_bf16, bool deterministic,
+                                    hipStream_t stream);
 void flowhip_zero_inject_fwd_launch(const float* inp, float* out, long total,
                                     int ih, int iw, int oh, int ow, int sH,
                                     int sW, hipStream_t stream);
@@ -109,7 +110,7 @@ void flowhip_seq_loss_bwd_launch(const float* const* preds, float* const* dst,
                                  float max_flow, float gamma, long numel_full,
                                  hipStream_t stream);
 bool flowhip_col_sum2_launch(const void* g, const void* x, float* out,
-                             long M, int C, int nchunk,
+                             float* partials, long M, int C, int nchunk,
                              hipStream_t stream);
 void flowhip_frozen_bn_apply_launch(const void* x, void* y, const float* s,
                                     const float* t, long M, int C,
@@ -118,7 +119,7 @@ int flowhip_plane_dot_sum_pchunks(long P, int B, int C);
 void flowhip_plane_dot_sum_launch(const float* x, const float* y,
                                   float* partials, float* out, long P, int B,
                                   int C, hipStream_t stream);
-bool flowhip_col_sum_launch(const void* dy, float* out,
+bool flowhip_col_sum_launch(const void* dy, float* out, float* partials,
                             long M, int C, int nchunk, hipStream_t stream);
 void flowhip_up2x_cat_fwd_launch(const float* low, const float* skip,
                                  float* out, long total, int C1, int C2,
@@ -584,19 +585,29 @@ torch::Tensor convex_up_fwd(torch::Tensor flow, torch::Tensor mask,
 
 std::vector<torch::Tensor> convex_up_bwd(torch::Tensor gout,
                                          torch::Tensor flow,
-                                         torch::Tensor mask, int64_t factor) {
+                                         torch::Tensor mask, int64_t factor,
+                                         bool deterministic) {
   TORCH_CHECK(gout.is_cuda() && gout.is_contiguous() &&
               gout.dtype() == torch::kFloat32);
   const int N = flow.size(0), H = flow.size(2), W = flow.size(3);
-  auto gflow = torch::zeros_like(flow);
+  // deterministic: per-pixel tap sums go to a scratch that a second kernel
+  // gathers in a fixed order; nothing is accumulated in place
+  auto gflow = deterministic ? torch::empty_like(flow)
+                             : torch::zeros_like(flow);
+  torch::Tensor contrib;
+  if (deterministic)
+    contrib = torch::empty({(long)N, (long)H, (long)W, 8, 9, 2},
+                           flow.options());
   auto gmask = torch::empty_like(mask);
   const c10::cuda::CUDAGuard guard(flow.device());
   hipStream_t stream = at::cuda::getCurrentCUDAStream().stream();
   flowhip_convex_up_bwd_launch(gout.data_ptr<float>(), flow.data_ptr<float>(),
                                mask.data_ptr<float>(),
                                gflow.data_ptr<float>(),
-                               gmask.data_ptr<float>(), N, H, W, (int)factor,
-                               stream);
+                               gmask.data_ptr<float>(),
+                               deterministic ? contrib.data_ptr<float>()
+                                             : nullptr,
+                               N, H, W, (int)factor, stream);
   return {gflow, gmask};
 }
 
@@ -952,7 +963,8 @@ torch::Tensor forward_splat(torch::Tensor flow, int64_t splits) {
   return out;
 }
 
-std::vector<torch::Tensor> instnorm_cl_fwd(torch::Tensor x, double eps) {
+std::vector<torch::Tensor> instnorm_cl_fwd(torch::Tensor x, double eps,
+                                           bool deterministic) {
   TORCH_CHECK(x.is_cuda() && x.dim() == 4);
   TORCH_CHECK(x.is_contiguous(torch::MemoryFormat::ChannelsLast),
               "instnorm_cl: channels_last input required");
@@ -974,12 +986,14 @@ std::vector<torch::Tensor> instnorm_cl_fwd(torch::Tensor x, double eps) {
                                  mean.data_ptr<float>(),
                                  rstd.data_ptr<float>(),
                                  partials.data_ptr<float>(), N, C, P,
-                                 (float)eps, bf16 ? 1 : 0, stream);
+                                 (float)eps, bf16 ? 1 : 0, deterministic,
+                                 stream);
   return {y, mean, rstd};
 }
 
 torch::Tensor instnorm_cl_bwd(torch::Tensor x, torch::Tensor dy,
-                              torch::Tensor mean, torch::Tensor rstd) {
+                              torch::Tensor mean, torch::Tensor rstd,
+                              bool deterministic) {
   const bool bf16 = x.scalar_type() == torch::kBFloat16;
   const int N = x.size(0), C = x.size(1);
   const long P = (long)x.size(2) * x.size(3);
@@ -998,7 +1012,8 @@ torch::Tensor instnorm_cl_bwd(torch::Tensor x, torch::Tensor dy,
                                  gmean.data_ptr<float>(),
                                  gxmean.data_ptr<float>(),
                                  partials.data_ptr<float>(), dx.data_ptr(),
-                                 N, C, P, bf16 ? 1 : 0, stream);
+                                 N, C, P, bf16 ? 1 : 0, deterministic,
+                                 stream);
   return dx;
 }
 
@@ -1410,19 +1425,26 @@ std::vector<torch::Tensor> conv_gemm_wrw_finish(
   return {dw, dbias};
 }
 
-torch::Tensor col_sum_bf16(torch::Tensor dy) {
+torch::Tensor col_sum_bf16(torch::Tensor dy, bool deterministic) {
   TORCH_CHECK(dy.is_cuda() && dy.dim() == 4 &&
               dy.scalar_type() == torch::kBFloat16 && dy.stride(1) == 1 &&
               dy.stride(3) == dy.size(1));
   const int C = dy.size(1);
   const long M = dy.numel() / C;
   const int nchunk = (int)((M + 255) / 256);  // must cover ALL rows (kernel bounds come from the chunk index)
-  auto out = torch::zeros({(long)C}, dy.options().dtype(torch::kFloat32));
+  const auto f32 = dy.options().dtype(torch::kFloat32);
+  // deterministic: one row per chunk, added in chunk order by a finish
+  // kernel; nothing accumulates in place, so nothing is zero-filled
+  auto out = deterministic ? torch::empty({(long)C}, f32)
+                           : torch::zeros({(long)C}, f32);
+  torch::Tensor partials;
+  if (deterministic) partials = torch::empty({(long)nchunk, (long)C}, f32);
   const c10::cuda::CUDAGuard guard(dy.device());
   hipStream_t stream = at::cuda::getCurrentCUDAStream().stream();
-  bool ok = flowhip_col_sum_launch(dy.data_ptr(),
-                                   out.data_ptr<float>(), M, C, nchunk,
-                                   stream);
+  bool ok = flowhip_col_sum_launch(
+      dy.data_ptr(), out.data_ptr<float>(),
+      deterministic ? partials.data_ptr<float>() : nullptr, M, C, nchunk,
+      stream);
   TORCH_CHECK(ok, "col_sum_bf16: C must be a multiple of 8");
   return out;
 }
@@ -1473,7 +1495,8 @@ torch::Tensor frozen_bn_apply(torch::Tensor x, torch::Tensor s,
   return y;
 }
 
-torch::Tensor col_sum2_bf16(torch::Tensor g, torch::Tensor x) {
+torch::Tensor col_sum2_bf16(torch::Tensor g, torch::Tensor x,
+                            bool deterministic) {
   TORCH_CHECK(g.is_cuda() && g.dim() == 4 &&
               g.scalar_type() == torch::kBFloat16 && g.stride(1) == 1 &&
               g.stride(3) == g.size(1));
@@ -1482,12 +1505,18 @@ torch::Tensor col_sum2_bf16(torch::Tensor g, torch::Tensor x) {
   const int C = g.size(1);
   const long M = g.numel() / C;
   const int nchunk = (int)((M + 255) / 256);
-  auto out = torch::zeros({2, (long)C}, g.options().dtype(torch::kFloat32));
+  const auto f32 = g.options().dtype(torch::kFloat32);
+  auto out = deterministic ? torch::empty({2, (long)C}, f32)
+                           : torch::zeros({2, (long)C}, f32);
+  torch::Tensor partials;
+  if (deterministic)
+    partials = torch::empty({(long)nchunk, 2, (long)C}, f32);
   const c10::cuda::CUDAGuard guard(g.device());
   hipStream_t stream = at::cuda::getCurrentCUDAStream().stream();
-  bool ok = flowhip_col_sum2_launch(g.data_ptr(), x.data_ptr(),
-                                    out.data_ptr<float>(), M, C, nchunk,
-                                    stream);
+  bool ok = flowhip_col_sum2_launch(
+      g.data_ptr(), x.data_ptr(), out.data_ptr<float>(),
+      deterministic ? partials.data_ptr<float>() : nullptr, M, C, nchunk,
+      stream);
   TORCH_CHECK(ok, "col_sum2_bf16: C must be a multiple of 8");
   return out;
 }
@@ -1771,7 +1800,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("corr_pyramid_bwd", &corr_pyramid_bwd,
         "fused pyramid backward combine -> dcorr");
   m.def("convex_up_fwd", &convex_up_fwd, "fused convex-combination upsample");
-  m.def("convex_up_bwd", &convex_up_bwd, "backward of convex_up_fwd");
+  m.def("convex_up_bwd", &convex_up_bwd, "backward of convex_up_fwd",
+        py::arg("gout"), py::arg("flow"), py::arg("mask"), py::arg("factor"),
+        py::arg("deterministic") = false);
   m.def("nconv_fwd", &nconv_fwd,
         "fused normalized convolution forward (out, cout)");
   m.def("plane_sum_nchw", &plane_sum_nchw,
@@ -1780,9 +1811,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("frozen_bn_apply", &frozen_bn_apply,
         "y = bf16(fp32(x)*s + t) per channel, channels-last");
   m.def("col_sum2_bf16", &col_sum2_bf16,
-        "(sum_m g, sum_m g*x) per channel in one pass (frozen-BN backward)");
+        "(sum_m g, sum_m g*x) per channel in one pass (frozen-BN backward)",
+        py::arg("g"), py::arg("x"), py::arg("deterministic") = false);
   m.def("col_sum_bf16", &col_sum_bf16,
-        "(N,C,H,W) channels-last bf16 -> (C) fp32 bias-grad column sum");
+        "(N,C,H,W) channels-last bf16 -> (C) fp32 bias-grad column sum",
+        py::arg("dy"), py::arg("deterministic") = false);
   m.def("up2x_cat_fwd", &up2x_cat_fwd,
         "fused nearest-2x upsample + channel concat");
   m.def("area_up2x_fwd", &area_up2x_fwd, "exact-2x area upsample");
@@ -1843,9 +1876,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("dw_into") = py::none(), py::arg("dbias_into") = py::none(),
         py::arg("path") = 0);
   m.def("instnorm_cl_fwd", &instnorm_cl_fwd,
-        "channels-last InstanceNorm2d forward (y, mean, rstd)");
+        "channels-last InstanceNorm2d forward (y, mean, rstd)",
+        py::arg("x"), py::arg("eps"), py::arg("deterministic") = false);
   m.def("instnorm_cl_bwd", &instnorm_cl_bwd,
-        "channels-last InstanceNorm2d backward");
+        "channels-last InstanceNorm2d backward", py::arg("x"), py::arg("dy"),
+        py::arg("mean"), py::arg("rstd"), py::arg("deterministic") = false);
   m.def("zero_inject_fwd", &zero_inject_fwd, "sparse injection scatter");
   m.def("zero_inject_bwd", &zero_inject_bwd, "backward gather of inject");
   m.def("forward_splat", &forward_splat,

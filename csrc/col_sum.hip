@@ -3,12 +3,18 @@
 // pixel dims of a channels-last tensor runs ~22 us for 5.5 MB (~100 calls
 // per step); this is a chunked 16-B-load reduction whose per-chunk rows
 // fold into the zero-filled output with one atomic per (chunk, channel).
+//
+// DET = true is the deterministic form (flowhip.ops.set_deterministic): the
+// p-streams fold in LDS with plain adds between barriers, each chunk writes
+// its row to a partials buffer, and col_sum_finish_kernel adds a column's
+// rows in an order fixed by indices alone. No atomics, nothing zero-filled.
 
 #include "common.h"
 
 #define CS_THREADS 256
 #define CS_MCHUNK 256  // small chunks: enough blocks to fill 256 CUs at M~21k
 
+template <bool DET>
 __global__ __launch_bounds__(CS_THREADS) void col_sum_partial_kernel(
     const __bf16* __restrict__ dy, float* __restrict__ out, long M,
     int C, int nchunk) {
@@ -40,22 +46,35 @@ __global__ __launch_bounds__(CS_THREADS) void col_sum_partial_kernel(
   for (int j = 0; j < 8; ++j)
     if (s < S && s < 32) red[(g * 8 + j) * 33 + s] = acc[j];
   __syncthreads();
-  if (s >= 32 && s < S)
-    for (int j = 0; j < 8; ++j)
-      atomicAdd(&red[(g * 8 + j) * 33 + (s & 31)], acc[j]);
-  __syncthreads();
+  if constexpr (DET) {
+    // streams 32r .. 32r+31 fold in round r: one thread per slot and round
+    for (int r = 1; r * 32 < S; ++r) {
+      if ((s >> 5) == r && s < S)
+        for (int j = 0; j < 8; ++j) red[(g * 8 + j) * 33 + (s & 31)] += acc[j];
+      __syncthreads();
+    }
+  } else {
+    if (s >= 32 && s < S)
+      for (int j = 0; j < 8; ++j)
+        atomicAdd(&red[(g * 8 + j) * 33 + (s & 31)], acc[j]);
+    __syncthreads();
+  }
   if (threadIdx.x < (unsigned)CBW) {
     float t = 0.f;
     const int smax = S < 32 ? S : 32;
     for (int ss = 0; ss < smax; ++ss) t += red[threadIdx.x * 33 + ss];
-    // one device-scope atomic per (chunk, channel) straight into the
-    // output (out is zero-filled by the caller): drops the separate
-    // finalize launch + the partials round trip (~10 us/call of
-    // latency-bound reduce across ~160 bias grads per step). Accumulation
-    // order across chunks is non-deterministic — like torch's own
-    // multi-block reductions; magnitudes are fp32 partial sums of
-    // comparable scale.
-    atomicAdd(&out[cb * 64 + threadIdx.x], t);
+    if constexpr (DET) {  // out = partials (nchunk, C)
+      out[(long)chunk * C + cb * 64 + threadIdx.x] = t;
+    } else {
+      // one device-scope atomic per (chunk, channel) straight into the
+      // output (out is zero-filled by the caller): drops the separate
+      // finalize launch + the partials round trip (~10 us/call of
+      // latency-bound reduce across ~160 bias grads per step). Accumulation
+      // order across chunks is non-deterministic — like torch's own
+      // multi-block reductions; magnitudes are fp32 partial sums of
+      // comparable scale.
+      atomicAdd(&out[cb * 64 + threadIdx.x], t);
+    }
   }
 }
 
@@ -64,6 +83,7 @@ __global__ __launch_bounds__(CS_THREADS) void col_sum_partial_kernel(
 // sum_m g[m,c]*x[m,c] in one pass over both tensors (torch's
 // native_batch_norm_backward spends ~105 us/call on the same reduction
 // pair at encoder shapes). out layout: (2, C), zero-filled by the caller.
+template <bool DET>
 __global__ __launch_bounds__(CS_THREADS) void col_sum2_partial_kernel(
     const __bf16* __restrict__ g, const __bf16* __restrict__ x,
     float* __restrict__ out, long M, int C, int nchunk) {
@@ -103,12 +123,23 @@ __global__ __launch_bounds__(CS_THREADS) void col_sum2_partial_kernel(
       red[1][(gi * 8 + j) * 33 + s] = agx[j];
     }
   __syncthreads();
-  if (s >= 32 && s < S)
-    for (int j = 0; j < 8; ++j) {
-      atomicAdd(&red[0][(gi * 8 + j) * 33 + (s & 31)], ag[j]);
-      atomicAdd(&red[1][(gi * 8 + j) * 33 + (s & 31)], agx[j]);
+  if constexpr (DET) {
+    for (int r = 1; r * 32 < S; ++r) {
+      if ((s >> 5) == r && s < S)
+        for (int j = 0; j < 8; ++j) {
+          red[0][(gi * 8 + j) * 33 + (s & 31)] += ag[j];
+          red[1][(gi * 8 + j) * 33 + (s & 31)] += agx[j];
+        }
+      __syncthreads();
     }
-  __syncthreads();
+  } else {
+    if (s >= 32 && s < S)
+      for (int j = 0; j < 8; ++j) {
+        atomicAdd(&red[0][(gi * 8 + j) * 33 + (s & 31)], ag[j]);
+        atomicAdd(&red[1][(gi * 8 + j) * 33 + (s & 31)], agx[j]);
+      }
+    __syncthreads();
+  }
   if (threadIdx.x < (unsigned)CBW) {
     const int smax = S < 32 ? S : 32;
     float t0 = 0.f, t1 = 0.f;
@@ -116,10 +147,41 @@ __global__ __launch_bounds__(CS_THREADS) void col_sum2_partial_kernel(
       t0 += red[0][threadIdx.x * 33 + ss];
       t1 += red[1][threadIdx.x * 33 + ss];
     }
-    // atomic chunk reduction straight into the zero-filled (2, C) output
-    // (see col_sum_partial_kernel)
-    atomicAdd(&out[cb * 64 + threadIdx.x], t0);
-    atomicAdd(&out[C + cb * 64 + threadIdx.x], t1);
+    if constexpr (DET) {  // out = partials (nchunk, 2, C)
+      out[((long)chunk * 2 + 0) * C + cb * 64 + threadIdx.x] = t0;
+      out[((long)chunk * 2 + 1) * C + cb * 64 + threadIdx.x] = t1;
+    } else {
+      // atomic chunk reduction straight into the zero-filled (2, C) output
+      // (see col_sum_partial_kernel)
+      atomicAdd(&out[cb * 64 + threadIdx.x], t0);
+      atomicAdd(&out[C + cb * 64 + threadIdx.x], t1);
+    }
+  }
+}
+
+
+// Deterministic finish: out[w] = sum over rows of partials (nrows, W), W = C
+// or 2*C. A block owns 16 columns; slice s adds rows s, s+16, ... in
+// ascending order (84 adds at the flagship's 1344 chunks), then one thread
+// per column adds the 16 slices in ascending order.
+#define CS_FIN_COLS 16
+#define CS_FIN_SLICES 16
+__global__ __launch_bounds__(CS_FIN_COLS * CS_FIN_SLICES)
+void col_sum_finish_kernel(const float* __restrict__ partials,
+                           float* __restrict__ out, int nrows, int W) {
+  const int col = blockIdx.x * CS_FIN_COLS + threadIdx.x % CS_FIN_COLS;
+  const int s = threadIdx.x / CS_FIN_COLS;
+  float acc = 0.f;
+  if (col < W)
+    for (int r = s; r < nrows; r += CS_FIN_SLICES)
+      acc += partials[(long)r * W + col];
+  __shared__ float red[CS_FIN_SLICES][CS_FIN_COLS + 1];
+  red[s][threadIdx.x % CS_FIN_COLS] = acc;
+  __syncthreads();
+  if (s == 0 && col < W) {
+    float t = 0.f;
+    for (int ss = 0; ss < CS_FIN_SLICES; ++ss) t += red[ss][threadIdx.x];
+    out[col] = t;
   }
 }
 
@@ -250,23 +312,46 @@ void flowhip_frozen_bn_apply_launch(const void* x, void* y, const float* s,
                      C / 8);
 }
 
+// partials == nullptr: the atomic form, `out` (2, C) zero-filled by the
+// caller. Otherwise the deterministic form: partials holds nchunk * 2 * C
+// floats, all written before they are read, and `out` needs no fill.
 bool flowhip_col_sum2_launch(const void* g, const void* x, float* out,
-                             long M, int C, int nchunk,
+                             float* partials, long M, int C, int nchunk,
                              hipStream_t stream) {
   if (C % 8 != 0 || C < 8) return false;
-  hipLaunchKernelGGL(col_sum2_partial_kernel, dim3(((C + 63) / 64) * nchunk),
-                     dim3(CS_THREADS), 0, stream, (const __bf16*)g,
-                     (const __bf16*)x, out, M, C, nchunk);
+  const dim3 grid(((C + 63) / 64) * nchunk);
+  if (partials) {
+    hipLaunchKernelGGL(col_sum2_partial_kernel<true>, grid, dim3(CS_THREADS),
+                       0, stream, (const __bf16*)g, (const __bf16*)x,
+                       partials, M, C, nchunk);
+    hipLaunchKernelGGL(col_sum_finish_kernel,
+                       dim3((2 * C + CS_FIN_COLS - 1) / CS_FIN_COLS),
+                       dim3(CS_FIN_COLS * CS_FIN_SLICES), 0, stream, partials,
+                       out, nchunk, 2 * C);
+    return true;
+  }
+  hipLaunchKernelGGL(col_sum2_partial_kernel<false>, grid, dim3(CS_THREADS),
+                     0, stream, (const __bf16*)g, (const __bf16*)x, out, M, C,
+                     nchunk);
   return true;
 }
 
-bool flowhip_col_sum_launch(const void* dy, float* out,
+bool flowhip_col_sum_launch(const void* dy, float* out, float* partials,
                             long M, int C, int nchunk, hipStream_t stream) {
   if (C % 8 != 0 || C < 8) return false;
+  const dim3 grid(((C + 63) / 64) * nchunk);
+  if (partials) {  // deterministic: (nchunk, C) rows, then the ordered finish
+    hipLaunchKernelGGL(col_sum_partial_kernel<true>, grid, dim3(CS_THREADS),
+                       0, stream, (const __bf16*)dy, partials, M, C, nchunk);
+    hipLaunchKernelGGL(col_sum_finish_kernel,
+                       dim3((C + CS_FIN_COLS - 1) / CS_FIN_COLS),
+                       dim3(CS_FIN_COLS * CS_FIN_SLICES), 0, stream, partials,
+                       out, nchunk, C);
+    return true;
+  }
   // `out` must be zero-filled (the binding allocates torch::zeros); the
   // chunk kernel reduces into it atomically — no finalize pass.
-  hipLaunchKernelGGL(col_sum_partial_kernel, dim3(((C + 63) / 64) * nchunk),
-                     dim3(CS_THREADS), 0, stream, (const __bf16*)dy,
-                     out, M, C, nchunk);
+  hipLaunchKernelGGL(col_sum_partial_kernel<false>, grid, dim3(CS_THREADS), 0,
+                     stream, (const __bf16*)dy, out, M, C, nchunk);
   return true;
 }

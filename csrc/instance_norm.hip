@@ -35,7 +35,13 @@
 // (the v2 per-lane-per-channel form was load-issue-bound at 427 us for a
 // 44 M-element plane; ~40 us is the bandwidth bound). Requires C % 8 == 0
 // (all extractor widths); the module falls back to torch otherwise.
-template <typename T, int MODE>
+//
+// DET = true (deterministic mode): the streams beyond 32 fold into the LDS
+// slots in rounds of 32 with plain adds between barriers, so a slot's adds
+// come in stream order. The atomic fold is order-free only while a slot
+// takes one add (column widths 32..64); at 8, 16 or 24 channels a slot
+// takes 2 to 7.
+template <typename T, int MODE, bool DET>
 __global__ __launch_bounds__(IN_THREADS) void instnorm_partial_kernel(
     const T* __restrict__ x, const T* __restrict__ a,
     const float* __restrict__ mean, float* __restrict__ partials,
@@ -105,14 +111,27 @@ __global__ __launch_bounds__(IN_THREADS) void instnorm_partial_kernel(
   }
   __syncthreads();
   // streams beyond 32 fold in (S can be 42 for CG=6... cap: accumulate)
-  if (s >= 32 && s < S) {
-    for (int j = 0; j < 8; ++j) {
-      const int c = g * 8 + j;
-      atomicAdd(&red[(c)*stride + (s & 31)], s1[j]);
-      atomicAdd(&red[(IN_CB + c) * stride + (s & 31)], s2[j]);
+  if constexpr (DET) {
+    for (int r = 1; r * 32 < S; ++r) {
+      if ((s >> 5) == r && s < S) {
+        for (int j = 0; j < 8; ++j) {
+          const int c = g * 8 + j;
+          red[(c)*stride + (s & 31)] += s1[j];
+          red[(IN_CB + c) * stride + (s & 31)] += s2[j];
+        }
+      }
+      __syncthreads();
     }
+  } else {
+    if (s >= 32 && s < S) {
+      for (int j = 0; j < 8; ++j) {
+        const int c = g * 8 + j;
+        atomicAdd(&red[(c)*stride + (s & 31)], s1[j]);
+        atomicAdd(&red[(IN_CB + c) * stride + (s & 31)], s2[j]);
+      }
+    }
+    __syncthreads();
   }
-  __syncthreads();
   if (threadIdx.x < (unsigned)CBW) {
     float t1 = 0.f, t2 = 0.f;
     const int smax = S < 32 ? S : 32;
@@ -208,10 +227,11 @@ int flowhip_instnorm_partial_rows(int N, int C, long P) {
 template <typename T>
 static void instnorm_fwd_t(const T* x, T* y, float* mean, float* rstd,
                            float* partials, int N, int C, long P, float eps,
-                           hipStream_t stream) {
+                           bool det, hipStream_t stream) {
   const int ncb = (C + IN_CB - 1) / IN_CB;
   const int nchunk = in_nchunk(P);
-  hipLaunchKernelGGL((instnorm_partial_kernel<T, 0>),
+  hipLaunchKernelGGL((det ? instnorm_partial_kernel<T, 0, true>
+                          : instnorm_partial_kernel<T, 0, false>),
                      dim3(N * ncb * nchunk), dim3(IN_THREADS), 0, stream, x,
                      (const T*)nullptr, (const float*)nullptr, partials, N, C,
                      P, nchunk);
@@ -229,10 +249,11 @@ template <typename T>
 static void instnorm_bwd_t(const T* x, const T* dy, const float* mean,
                            const float* rstd, float* gmean, float* gxmean,
                            float* partials, T* dx, int N, int C, long P,
-                           hipStream_t stream) {
+                           bool det, hipStream_t stream) {
   const int ncb = (C + IN_CB - 1) / IN_CB;
   const int nchunk = in_nchunk(P);
-  hipLaunchKernelGGL((instnorm_partial_kernel<T, 1>),
+  hipLaunchKernelGGL((det ? instnorm_partial_kernel<T, 1, true>
+                          : instnorm_partial_kernel<T, 1, false>),
                      dim3(N * ncb * nchunk), dim3(IN_THREADS), 0, stream, x,
                      dy, mean, partials, N, C, P, nchunk);
   hipLaunchKernelGGL(instnorm_finalize_bwd_kernel, dim3(N * ncb), dim3(64), 0,
@@ -248,25 +269,27 @@ static void instnorm_bwd_t(const T* x, const T* dy, const float* mean,
 void flowhip_instnorm_cl_fwd_launch(const void* x, void* y, float* mean,
                                     float* rstd, float* partials, int N,
                                     int C, long P, float eps, int is_bf16,
-                                    hipStream_t stream) {
+                                    bool deterministic, hipStream_t stream) {
   if (is_bf16)
     instnorm_fwd_t((const __hip_bfloat16*)x, (__hip_bfloat16*)y, mean, rstd,
-                   partials, N, C, P, eps, stream);
+                   partials, N, C, P, eps, deterministic, stream);
   else
     instnorm_fwd_t((const float*)x, (float*)y, mean, rstd, partials, N, C, P,
-                   eps, stream);
+                   eps, deterministic, stream);
 }
 
 void flowhip_instnorm_cl_bwd_launch(const void* x, const void* dy,
                                     const float* mean, const float* rstd,
                                     float* gmean, float* gxmean,
                                     float* partials, void* dx, int N, int C,
-                                    long P, int is_bf16, hipStream_t stream) {
+                                    long P, int is_bf16, bool deterministic,
+                                    hipStream_t stream) {
   if (is_bf16)
     instnorm_bwd_t((const __hip_bfloat16*)x, (const __hip_bfloat16*)dy, mean,
                    rstd, gmean, gxmean, partials, (__hip_bfloat16*)dx, N, C,
-                   P, stream);
+                   P, deterministic, stream);
   else
     instnorm_bwd_t((const float*)x, (const float*)dy, mean, rstd, gmean,
-                   gxmean, partials, (float*)dx, N, C, P, stream);
+                   gxmean, partials, (float*)dx, N, C, P, deterministic,
+                   stream);
 }

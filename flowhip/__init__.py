@@ -19,3 +19,5 @@ Layers (bottom-up): utils -> ops -> nn -> models -> engine.
 __version__ = "0.1.0"
 
 from . import utils  # noqa: F401
+from .ops import (deterministic, deterministic_enabled,  # noqa: F401
+                  set_deterministic)

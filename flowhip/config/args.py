@@ -215,6 +215,10 @@ def build_train_parser(argv=None):
     parser.add_argument("--alternate_corr", action="store_true",
                         help="on-demand correlation lookup (no all-pairs "
                         "volume; memory-bounded, for large frames)")
+    parser.add_argument("--deterministic", action="store_true",
+                        help="bit-reproducible training step: atomics-free "
+                        "HIP kernels (flowhip.set_deterministic) and "
+                        "torch.use_deterministic_algorithms(warn_only=True)")
     parser.add_argument("--profile_dir", default=None,
                         help="rank-0 torch.profiler capture: wait 1 / warmup "
                         "2 / active 3 steps, chrome trace + op table written "

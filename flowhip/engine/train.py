@@ -92,7 +92,17 @@ def _make_profiler(out_dir):
         on_trace_ready=_on_ready)
 
 
+def apply_deterministic(args):
+    """--deterministic: turn on the HIP kernels' deterministic mode, and
+    have torch name (warn_only) every op of its own that has no
+    deterministic implementation, e.g. --small's bilinear upflow8 backward."""
+    if getattr(args, "deterministic", False):
+        ops.set_deterministic(True)
+        torch.use_deterministic_algorithms(True, warn_only=True)
+
+
 def train(args):
+    apply_deterministic(args)
     rank, world_size, device = distributed.init_distributed()
 
     torch.manual_seed(args.seed)

@@ -12,12 +12,14 @@ import torch
 import torch.nn as nn
 
 from ..ops import _ext
+from ..ops.determinism import deterministic_enabled
 
 
 class _InstNormCLFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, eps):
-        y, mean, rstd = _ext.ext().instnorm_cl_fwd(x, eps)
+        y, mean, rstd = _ext.ext().instnorm_cl_fwd(
+            x, eps, deterministic=deterministic_enabled())
         ctx.save_for_backward(x, mean, rstd)
         return y
 
@@ -25,7 +27,8 @@ class _InstNormCLFn(torch.autograd.Function):
     def backward(ctx, dy):
         x, mean, rstd = ctx.saved_tensors
         dy = dy.contiguous(memory_format=torch.channels_last)
-        return _ext.ext().instnorm_cl_bwd(x, dy, mean, rstd), None
+        return _ext.ext().instnorm_cl_bwd(
+            x, dy, mean, rstd, deterministic=deterministic_enabled()), None
 
 
 class InstanceNorm2d(nn.InstanceNorm2d):
@@ -67,7 +70,8 @@ class _FrozenBNFn(torch.autograd.Function):
         if g.dtype != torch.bfloat16:
             g = g.to(torch.bfloat16)
         sums = _ext.ext().col_sum2_bf16(
-            g, x if x.dtype == torch.bfloat16 else x.to(torch.bfloat16))
+            g, x if x.dtype == torch.bfloat16 else x.to(torch.bfloat16),
+            deterministic=deterministic_enabled())
         db = sums[0]
         dw = (sums[1] - rm.float() * db) * invstd
         dx = _ext.ext().frozen_bn_apply(g, s, None)

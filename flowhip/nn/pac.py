@@ -235,14 +235,9 @@ def pacpool2d(input, kernel, kernel_size, stride=1, padding=0, dilation=1):
     kernel_size = _pair(kernel_size)
     bs, in_ch = input.shape[:2]
 
-    from ..ops import _ext
-    from ..ops.functional_pac import PacPool2dFn
+    from ..ops.functional_pac import PacPool2dFn, pac_pool_fusable
     s, p, d = _pair(stride), _pair(padding), _pair(dilation)
-    if (input.is_cuda and input.dtype == torch.float32
-            and kernel.dtype == torch.float32
-            and _ext.ext() is not None and not _ext.force_ref()
-            and kernel_size[0] == kernel_size[1] and d[0] == d[1]
-            and kernel.dim() >= 5):
+    if pac_pool_fusable(input, kernel, kernel_size, d):
         K = kernel_size[0]
         kr = kernel.reshape(bs, -1, K * K, *kernel.shape[-2:])
         if kr.shape[1] in (1, in_ch):

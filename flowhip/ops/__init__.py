@@ -16,11 +16,17 @@ SURVEY.md §2.2 kernel inventory):
   convex_upsample(flow, mask)          kernel #11 (RAFT convex upsample)
   forward_splat(flow)                  warm-start nearest splat (no gradient)
   sequence_loss(preds, gt, valid, g)   kernel #12 (loss; torch for now)
+
+  set_deterministic(flag) / deterministic_enabled() / deterministic(flag)
+                                       bit-reproducible training step
+                                       (ops/determinism.py)
 """
 
 import torch
 
 from . import _ext, torch_ref
+from .determinism import (deterministic, deterministic_enabled,  # noqa: F401
+                          set_deterministic)
 from .torch_ref import MAX_FLOW  # re-export  # noqa: F401
 
 

@@ -19,6 +19,7 @@ import os
 import torch
 
 from . import _ext
+from .determinism import deterministic_enabled
 
 
 def _pad_k(t):
@@ -263,7 +264,8 @@ class AltCorrLookupFn(torch.autograd.Function):
     backward returns gradients for fmap1 and fmap2 from `alt_corr_lookup_bwd`
     (csrc/alt_corr_bwd.hip): the transposed window blend per (pixel, level),
     df1 rows summed in registers, level gradients of f2 summed with float
-    atomics into fp32 accumulators (so df2 is not bit-reproducible) and
+    atomics into fp32 accumulators (so df2 is not bit-reproducible; in
+    deterministic mode a backward that needs df2 raises) and
     gathered back through the pooling chain by one kernel. It allocates
     df1, df2 and the level accumulators, about 3.33 * P * D * 4 bytes, and
     nothing that grows with P^2. `needs_input_grad` selects what is
@@ -299,6 +301,14 @@ class AltCorrLookupFn(torch.autograd.Function):
         need1, need2 = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
         if not (need1 or need2):
             return (None,) * (5 + len(levels))
+        if need2 and deterministic_enabled():
+            raise RuntimeError(
+                "alt_corr_lookup backward: the on-demand lookup's df2 (the "
+                "gradient of fmap2) does not have a deterministic "
+                "implementation, but deterministic mode is on "
+                "(flowhip.set_deterministic / FLOWHIP_DETERMINISTIC / "
+                "--deterministic). Turn the mode off for this operation, or "
+                "train without --alternate_corr.")
         mode = os.environ.get("FLOWHIP_ALT_CORR_BWD", "") or "auto"
         if mode not in ("auto", "torch", "direct", "tiled"):
             raise ValueError(

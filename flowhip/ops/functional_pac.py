@@ -8,6 +8,7 @@ implementation in flowhip/nn/pac.py.
 import torch
 
 from . import _ext
+from .determinism import deterministic_enabled
 
 
 class PacKernelGaussFn(torch.autograd.Function):
@@ -74,9 +75,25 @@ class PacPool2dFn(torch.autograd.Function):
         return dx, dk, None, None, None, None, None, None
 
 
+def pac_pool_fusable(input, kernel, kernel_size, dilation):
+    """True where pacpool2d runs PacPool2dFn (whose dx is an atomic
+    scatter, so deterministic mode keeps it on the torch path)."""
+    return (not deterministic_enabled()
+            and input.is_cuda and input.dtype == torch.float32
+            and kernel.dtype == torch.float32
+            and _ext.ext() is not None and not _ext.force_ref()
+            and kernel_size[0] == kernel_size[1]
+            and dilation[0] == dilation[1]
+            and kernel.dim() >= 5)
+
+
 def pac_kernel_fusable(input, mask, kernel_type, smooth_kernel_type,
                        channel_wise, kernel_size, dilation, eff_stride,
                        eff_padding):
+    # deterministic mode: the PAC kernels' backward sums with atomics, so
+    # the heads take the torch implementation in flowhip/nn/pac.py
+    if deterministic_enabled():
+        return False
     K = kernel_size[0]
     d = dilation[0]
     return (input.is_cuda and input.dtype == torch.float32
@@ -92,6 +109,8 @@ def pac_kernel_fusable(input, mask, kernel_type, smooth_kernel_type,
 
 def pac_conv_fusable(x, kernel, weight, stride, padding, dilation):
     K = weight.shape[-1]
+    if deterministic_enabled():
+        return False
     if not (x.is_cuda and x.dtype == torch.float32
             and _ext.ext() is not None and not _ext.force_ref()):
         return False

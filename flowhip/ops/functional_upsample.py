@@ -4,6 +4,7 @@
 import torch
 
 from . import _ext
+from .determinism import deterministic_enabled
 
 
 class ConvexUpsampleFn(torch.autograd.Function):
@@ -19,8 +20,9 @@ class ConvexUpsampleFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout):
         flow, mask = ctx.saved_tensors
-        gflow, gmask = _ext.ext().convex_up_bwd(gout.contiguous(), flow, mask,
-                                                ctx.factor)
+        gflow, gmask = _ext.ext().convex_up_bwd(
+            gout.contiguous(), flow, mask, ctx.factor,
+            deterministic=deterministic_enabled())
         return gflow, gmask, None
 
 
