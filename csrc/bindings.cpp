@@ -85,6 +85,12 @@ void flowhip_forward_splat_plan(int H, int W, int splits, int* chunk_out,
 void flowhip_forward_splat_launch(const float* flow, float* out, double* ws_d,
                                   int* ws_i, int B, int H, int W, int chunk,
                                   int G, hipStream_t stream);
+int flowhip_fb_consistency_blocks(int H, int W);
+void flowhip_fb_consistency_launch(const float* flow_fw, const float* flow_bw,
+                                   unsigned char* occ, float* res,
+                                   double* partials, double* stats, int N,
+                                   int H, int W, double alpha1, double alpha2,
+                                   hipStream_t stream);
 void flowhip_gru_gate1_fwd_launch(const void* zr, const void* h, void* z,
                                   void* rh, long total, int C, long P,
                                   int is_bf16, int cl, hipStream_t stream);
@@ -961,6 +967,45 @@ torch::Tensor forward_splat(torch::Tensor flow, int64_t splits) {
       G > 1 ? ws_i.data_ptr<int>() : nullptr, (int)B, (int)H, (int)W, chunk,
       G, stream);
   return out;
+}
+
+// Forward-backward consistency of a bidirectional flow pair, both directions
+// in one launch: two (N,2,H,W) fp32 flows -> {occ_fw, occ_bw} uint8 (N,1,H,W),
+// {res_fw, res_bw} fp32 (N,1,H,W), stats fp64 (N,2,4).
+std::vector<torch::Tensor> fb_consistency(torch::Tensor flow_fw,
+                                          torch::Tensor flow_bw, double alpha1,
+                                          double alpha2) {
+  TORCH_CHECK(flow_fw.is_cuda() && flow_bw.is_cuda() &&
+                  flow_fw.device() == flow_bw.device() &&
+                  flow_fw.dtype() == torch::kFloat32 &&
+                  flow_bw.dtype() == torch::kFloat32 && flow_fw.dim() == 4 &&
+                  flow_fw.size(1) == 2 && flow_fw.sizes() == flow_bw.sizes(),
+              "fb_consistency: two (N,2,H,W) fp32 CUDA tensors of one shape "
+              "required");
+  auto f = flow_fw.contiguous();
+  auto b = flow_bw.contiguous();
+  const int64_t N = f.size(0), H = f.size(2), W = f.size(3);
+  TORCH_CHECK(H >= 2 && W >= 2, "fb_consistency: H and W must be >= 2");
+  // the kernel indexes a plane with int and overshoots it by up to one
+  // workgroup of pixels
+  TORCH_CHECK(H * W < (int64_t(1) << 31) - 4096,
+              "fb_consistency: H*W must stay below 2^31");
+  TORCH_CHECK(N <= 65535, "fb_consistency: batch exceeds the grid limit");
+  auto occ = torch::empty({2, N, 1, H, W}, f.options().dtype(torch::kUInt8));
+  auto res = torch::empty({2, N, 1, H, W}, f.options());
+  auto stats = torch::empty({N, 2, 4}, f.options().dtype(torch::kFloat64));
+  if (N > 0) {
+    const int nblk = flowhip_fb_consistency_blocks((int)H, (int)W);
+    auto partials = torch::empty({2, N, (int64_t)nblk, 4}, stats.options());
+    const c10::cuda::CUDAGuard guard(f.device());
+    hipStream_t stream = at::cuda::getCurrentCUDAStream().stream();
+    flowhip_fb_consistency_launch(
+        f.data_ptr<float>(), b.data_ptr<float>(), occ.data_ptr<uint8_t>(),
+        res.data_ptr<float>(), partials.data_ptr<double>(),
+        stats.data_ptr<double>(), (int)N, (int)H, (int)W, alpha1, alpha2,
+        stream);
+  }
+  return {occ[0], occ[1], res[0], res[1], stats};
 }
 
 std::vector<torch::Tensor> instnorm_cl_fwd(torch::Tensor x, double eps,
@@ -1890,6 +1935,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("forward_splat_plan", &forward_splat_plan,
         "source chunk count G the splat uses for an (H, W) field",
         py::arg("H"), py::arg("W"), py::arg("splits") = 0);
+  m.def("fb_consistency", &fb_consistency,
+        "forward-backward consistency check of a bidirectional flow pair -> "
+        "[occ_fw, occ_bw, res_fw, res_bw, stats]",
+        py::arg("flow_fw"), py::arg("flow_bw"), py::arg("alpha1") = 0.01,
+        py::arg("alpha2") = 0.5);
   m.def("gru_gate1_fwd", &gru_gate1_fwd, "fused GRU z/r gates + r*h");
   m.def("gru_gate1_bwd", &gru_gate1_bwd, "backward of gru_gate1");
   m.def("gru_gate2_fwd", &gru_gate2_fwd, "fused GRU tanh + lerp update");

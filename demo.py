@@ -7,7 +7,13 @@ As in the reference, --model is the CHECKPOINT path; the architecture is
 selected with --arch (reference hardcoded RAFT).
 
     python demo.py --model ckpt.pth --path frames_dir [--out demo_out]
-                   [--warm_start]
+                   [--warm_start] [--bidirectional]
+
+--bidirectional estimates both directions of every pair in one pass and
+writes, per pair, flow_%04d.png (1->2), flow_bw_%04d.png (2->1) and
+occ_%04d.png: the forward-backward occlusion mask of the 1->2 flow as an
+8-bit image, 255 = occluded (`ops.fb_consistency` on the unpadded flows). One
+log line per pair gives the visible share and the mean visible residual.
 """
 
 import argparse
@@ -18,6 +24,7 @@ import numpy as np
 import torch
 from PIL import Image
 
+from flowhip import ops
 from flowhip.config import add_ncup_module_flags, finalize_args
 from flowhip.data import flow_viz
 from flowhip.engine import checkpoints
@@ -50,6 +57,20 @@ def viz(img, flo, out_path):
     Image.fromarray(img_flo).save(out_path)
 
 
+def write_occlusion(flow_fw, flow_bw, out_path):
+    """Forward-backward check of one unpadded pair: writes the 1->2 occlusion
+    mask (255 = occluded) and returns the log line."""
+    occ_fw, _, _, _, stats = ops.fb_consistency(flow_fw, flow_bw)
+    Image.fromarray((occ_fw[0, 0] * 255).cpu().numpy()).save(out_path)
+    npix = flow_fw.shape[-2] * flow_fw.shape[-1]
+    visible, _, _, rsum = stats[0].cpu().unbind(-1)     # (fw, bw) each
+    mean = rsum / visible.clamp(min=1)
+    return ("%s: visible %.1f%% fw / %.1f%% bw, mean visible residual "
+            "%.3f px fw / %.3f px bw"
+            % (os.path.basename(out_path), 100 * visible[0] / npix,
+               100 * visible[1] / npix, mean[0], mean[1]))
+
+
 def demo(args):
     model_args = finalize_args(args)
     model_args.model = args.arch
@@ -67,12 +88,24 @@ def demo(args):
 
         # --warm_start: the frames are one sequence; each pair starts from
         # the previous pair's flow, splatted forward on the device
-        stream = FlowStream(model, iters=20, warm_start=args.warm_start)
+        stream = FlowStream(model, iters=20, warm_start=args.warm_start,
+                            bidirectional=args.bidirectional)
         for i, (image1, image2) in enumerate(zip(images[:-1], images[1:])):
             padder = InputPadder(image1.shape)
             image1, image2 = padder.pad(image1, image2)
             flow_low, flow_up = stream.step(image1, image2)
-            viz(image1, flow_up, os.path.join(args.out, "flow_%04d.png" % i))
+            if not args.bidirectional:
+                viz(image1, flow_up,
+                    os.path.join(args.out, "flow_%04d.png" % i))
+                continue
+            n = image1.shape[0]
+            viz(image1, flow_up[:n],
+                os.path.join(args.out, "flow_%04d.png" % i))
+            viz(image2, flow_up[n:],
+                os.path.join(args.out, "flow_bw_%04d.png" % i))
+            print(write_occlusion(
+                padder.unpad(flow_up[:n]), padder.unpad(flow_up[n:]),
+                os.path.join(args.out, "occ_%04d.png" % i)))
 
 
 def build_parser():
@@ -90,6 +123,10 @@ def build_parser():
                         help="treat the frames as one sequence: start each "
                         "pair from the previous pair's flow (device-side "
                         "nearest splat)")
+    parser.add_argument("--bidirectional", action="store_true",
+                        help="estimate both directions of every pair and "
+                        "write the backward flow and the forward-backward "
+                        "occlusion mask (255 = occluded) next to the flow")
     add_ncup_module_flags(parser)
     return parser
 

@@ -13,6 +13,7 @@ device, and no host syncs occur in the loop.
 import torch
 
 from .. import ops
+from .stream import warm_init
 
 
 class GraphedInference:
@@ -31,13 +32,27 @@ class GraphedInference:
         g = GraphedInference(model, shape, iters=32, warm_start=True)
         flow_low, flow_up = g(image1, image2)                # cold
         flow_low, flow_up = g(image2, image3, g.next_init)   # warm
+
+    bidirectional=True captures the bidirectional forward: the outputs (and
+    `flow_init` / `next_init`) have batch 2N, the 1->2 flow first. With
+    consistency=True the same graph also runs `ops.fb_consistency` on the two
+    halves of `flow_up`; its five results are the static buffers
+    `self.consistency` (occ_fw, occ_bw, res_fw, res_bw, stats), valid after
+    each call like the outputs. The check covers the captured shape: callers
+    with padded frames unpad the flows and call the op themselves.
     """
 
-    def __init__(self, model, input_shape, iters, warmup=3, warm_start=False):
+    def __init__(self, model, input_shape, iters, warmup=3, warm_start=False,
+                 bidirectional=False, consistency=False):
         assert torch.cuda.is_available(), "hipGraph capture requires a GPU"
+        if consistency and not bidirectional:
+            raise ValueError("consistency=True needs bidirectional=True")
         self.model = model.eval()
         self.iters = iters
         self.warm_start = warm_start
+        self.bidirectional = bidirectional
+        self.check = consistency
+        self.consistency = None
         device = next(model.parameters()).device
 
         self.static_img1 = torch.zeros(input_shape, device=device)
@@ -46,6 +61,8 @@ class GraphedInference:
         self.next_init = None
         if warm_start:
             b, _, h, w = input_shape
+            if bidirectional:
+                b = 2 * b
             self.static_init = torch.zeros((b, 2, h // 8, w // 8),
                                            device=device)
 
@@ -62,10 +79,23 @@ class GraphedInference:
             self.static_out = self._forward()
 
     def _forward(self):
+        if self.bidirectional:
+            return self._forward_bidirectional()
         out = self.model(self.static_img1, self.static_img2, iters=self.iters,
                          flow_init=self.static_init, test_mode=True)
         if self.warm_start:
             self.next_init = ops.forward_splat(out[0])
+        return out
+
+    def _forward_bidirectional(self):
+        out = self.model(self.static_img1, self.static_img2, iters=self.iters,
+                         flow_init=self.static_init, test_mode=True,
+                         bidirectional=True)
+        if self.warm_start:
+            self.next_init = warm_init(out[0], bidirectional=True)
+        if self.check:
+            n = self.static_img1.shape[0]
+            self.consistency = ops.fb_consistency(out[1][:n], out[1][n:])
         return out
 
     @torch.no_grad()

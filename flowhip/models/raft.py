@@ -92,15 +92,58 @@ class RAFT(nn.Module):
         inp = to_model_layout(torch.relu(inp))
         return image1, corr_fn, net, inp
 
+    def _features_bidirectional(self, image1, image2):
+        """`_features` for both directions at once, batch 2N: the first N
+        samples are the pair (image1, image2), the last N (image2, image1).
+        The feature network still sees each frame once; the correlation is
+        built on the two stacked orders of its outputs."""
+        from ..utils.layout import to_model_layout
+        image1 = 2 * (image1 / 255.0) - 1.0
+        image2 = 2 * (image2 / 255.0) - 1.0
+        image1 = to_model_layout(image1)
+        image2 = to_model_layout(image2)
+
+        fmap1, fmap2 = self.fnet([image1, image2])
+
+        with autocast_off_ctx(image1):
+            fmap1 = fmap1.float()
+            fmap2 = fmap2.float()
+            fmap12 = torch.cat([fmap1, fmap2], dim=0)
+            fmap21 = torch.cat([fmap2, fmap1], dim=0)
+            if getattr(self.args, "alternate_corr", False):
+                corr_fn = AlternateCorrBlock(fmap12, fmap21,
+                                             radius=self.args.corr_radius)
+            else:
+                corr_fn = CorrBlock(fmap12, fmap21,
+                                    radius=self.args.corr_radius)
+
+        images = to_model_layout(torch.cat([image1, image2], dim=0))
+        cnet = self.cnet(images)
+        net, inp = torch.split(cnet, [self.hidden_dim, self.context_dim], dim=1)
+        net = to_model_layout(torch.tanh(net))
+        inp = to_model_layout(torch.relu(inp))
+        return images, corr_fn, net, inp
+
     def forward(self, image1, image2, iters=12, flow_init=None, upsample=True,
-                test_mode=False):
+                test_mode=False, bidirectional=False):
         """Estimate optical flow between a pair of frames.
 
         `upsample` is accepted for API compatibility and ignored, as in the
         reference (raft.py:87 — SURVEY.md §2.9 quirk 4).
+
+        bidirectional=True (test_mode only) estimates both directions in one
+        pass at batch 2N: the returned (flow_low, flow_up) hold the 1->2 flow
+        in their first N samples and the 2->1 flow in their last N; a
+        `flow_init` is (2N, 2, H/8, W/8) in the same order.
         """
+        if bidirectional and not test_mode:
+            raise ValueError("bidirectional=True needs test_mode=True")
         with autocast_ctx(image1, enabled=self.args.mixed_precision):
-            image1, corr_fn, net, inp = self._features(image1, image2)
+            if bidirectional:
+                image1, corr_fn, net, inp = self._features_bidirectional(
+                    image1, image2)
+            else:
+                image1, corr_fn, net, inp = self._features(image1, image2)
 
             coords0, coords1 = self.initialize_flow(image1)
             if flow_init is not None:

@@ -54,9 +54,17 @@ class RAFT_NC_DBL(_RAFTBase):
         return self.upsampler(flow_lr, guidance.contiguous())
 
     def forward(self, image1, image2, iters=12, flow_init=None, upsample=True,
-                test_mode=False):
+                test_mode=False, bidirectional=False):
+        """bidirectional=True (test_mode only): both directions in one pass
+        at batch 2N, 1->2 first, as in `RAFT.forward`."""
+        if bidirectional and not test_mode:
+            raise ValueError("bidirectional=True needs test_mode=True")
         with autocast_ctx(image1, enabled=self.args.mixed_precision):
-            image1, corr_fn, net, inp = self._features(image1, image2)
+            if bidirectional:
+                image1, corr_fn, net, inp = self._features_bidirectional(
+                    image1, image2)
+            else:
+                image1, corr_fn, net, inp = self._features(image1, image2)
 
             coords0, coords1 = self.initialize_flow(image1)
             if flow_init is not None:

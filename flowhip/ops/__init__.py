@@ -15,6 +15,7 @@ SURVEY.md §2.2 kernel inventory):
   zero_inject(x, sh, sw)               kernel #8  (sparse injection scatter)
   convex_upsample(flow, mask)          kernel #11 (RAFT convex upsample)
   forward_splat(flow)                  warm-start nearest splat (no gradient)
+  fb_consistency(flow_fw, flow_bw)     forward-backward occlusion check
   sequence_loss(preds, gt, valid, g)   kernel #12 (loss; torch for now)
 
   set_deterministic(flag) / deterministic_enabled() / deterministic(flag)
@@ -239,6 +240,24 @@ def forward_splat(flow, splits=0):
             return ForwardSplatFn.apply(flow[None], splits)[0]
         return ForwardSplatFn.apply(flow, splits)
     return torch_ref.forward_splat(flow)
+
+
+def fb_consistency(flow_fw, flow_bw, alpha1=0.01, alpha2=0.5):
+    """Forward-backward consistency check of a bidirectional flow pair:
+    `flow_fw` (1->2, on frame 1's grid) and `flow_bw` (2->1, on frame 2's
+    grid), both (N,2,H,W) with H, W >= 2.
+
+    Returns (occ_fw, occ_bw, res_fw, res_bw, stats): uint8 occlusion masks
+    (1 = occluded, out of frame or non-finite), fp32 residuals |f + b~| and
+    fp64 (N,2,4) per-sample, per-direction counts and visible residual sum —
+    the definition is `torch_ref.fb_consistency`'s. The defaults are the
+    UnFlow thresholds. Not differentiable. HIP for CUDA fp32 tensors (any
+    strides); the float64 twin otherwise."""
+    if (_ext.use_hip(flow_fw) and flow_bw.is_cuda
+            and flow_fw.dtype == flow_bw.dtype == torch.float32):
+        return tuple(_ext.ext().fb_consistency(
+            flow_fw.detach(), flow_bw.detach(), float(alpha1), float(alpha2)))
+    return torch_ref.fb_consistency(flow_fw, flow_bw, alpha1, alpha2)
 
 
 def convex_upsample(flow, mask, factor=8):

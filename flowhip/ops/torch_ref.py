@@ -8,7 +8,7 @@ These serve three roles:
      into the reference repo.
 
 Every function here is differentiable through torch autograd, except
-`forward_splat` (a nearest-source selection).
+`forward_splat` (a nearest-source selection) and `fb_consistency` (a mask).
 """
 
 import math
@@ -290,6 +290,106 @@ def forward_splat(flow, return_ties=False, max_pairs=1 << 22):
     if squeeze:
         out, ties = out[0], ties[0]
     return (out, ties) if return_ties else out
+
+
+# ---------------------------------------------------------------------------
+# Forward-backward consistency check (occlusion mask of a bidirectional pair)
+# ---------------------------------------------------------------------------
+
+def _fb_one_direction(f, b, alpha1, alpha2):
+    """`f` (N,2,H,W) float64 checked against `b`; see fb_consistency."""
+    N, _, H, W = f.shape
+    HW = H * W
+    dev = f.device
+    gy, gx = torch.meshgrid(
+        torch.arange(H, device=dev, dtype=torch.float64),
+        torch.arange(W, device=dev, dtype=torch.float64), indexing="ij")
+    fx, fy = f[:, 0], f[:, 1]
+    px = gx + fx
+    py = gy + fy
+    inframe = (px >= 0) & (px <= W - 1) & (py >= 0) & (py <= H - 1)
+    # out-of-frame lanes sample (0, 0): computed, then masked out below
+    px = torch.where(inframe, px, 0.0)
+    py = torch.where(inframe, py, 0.0)
+    x0 = px.floor().clamp(max=W - 2)
+    y0 = py.floor().clamp(max=H - 2)
+    wx = px - x0
+    wy = py - y0
+    i00 = (y0 * W + x0).long().reshape(N, 1, HW).expand(N, 2, HW)
+    bb = b.reshape(N, 2, HW)
+
+    def tap(off):
+        return torch.gather(bb, 2, i00 + off).reshape(N, 2, H, W)
+
+    wx, wy = wx[:, None], wy[:, None]
+    top = tap(0) * (1.0 - wx) + tap(1) * wx
+    bot = tap(W) * (1.0 - wx) + tap(W + 1) * wx
+    bs = top * (1.0 - wy) + bot * wy
+    bx, by = bs[:, 0], bs[:, 1]
+
+    sx = fx + bx
+    sy = fy + by
+    r2 = sx * sx + sy * sy
+    thr = alpha1 * ((fx * fx + fy * fy) + (bx * bx + by * by)) + alpha2
+    finite = inframe & torch.isfinite(r2) & torch.isfinite(thr)
+    visible = finite & (r2 <= thr)
+    r = torch.where(finite, r2, 0.0).sqrt()
+    occ = (~visible).to(torch.uint8)[:, None]
+    res = torch.where(finite, r, float("inf")).float()[:, None]
+    stats = torch.stack([
+        visible.sum(dim=(1, 2)).double(),
+        (finite & ~visible).sum(dim=(1, 2)).double(),
+        (~finite).sum(dim=(1, 2)).double(),
+        torch.where(visible, r, 0.0).sum(dim=(1, 2))], dim=1)
+    gap = torch.where(finite, (r2 - thr).abs(), float("inf"))
+    return occ, res, stats, gap.min()
+
+
+@torch.no_grad()
+def fb_consistency(flow_fw, flow_bw, alpha1=0.01, alpha2=0.5,
+                   return_margin=False):
+    """Forward-backward consistency of a bidirectional flow pair (the UnFlow
+    occlusion test). No gradient.
+
+    `flow_fw` is the 1->2 flow on frame 1's grid, `flow_bw` the 2->1 flow on
+    frame 2's grid, both (N, 2, H, W), channel 0 = x, H, W >= 2. One
+    direction, `f` checked against `b`, in float64 on the inputs' values,
+    every operation rounded on its own:
+
+        p   = (x + f_x, y + f_y)
+        in frame iff 0 <= p_x <= W-1 and 0 <= p_y <= H-1 (false for NaN)
+        b~  = bilinear sample of b at p: x0 = min(floor(p_x), W-2),
+              w_x = p_x - x0, same in y; all four taps are read, so a
+              non-finite tap makes b~ non-finite even at weight 0
+              top = b00*(1-w_x) + b01*w_x, bot likewise, b~ = top*(1-w_y) + bot*w_y
+        r2  = (f_x + b~_x)^2 + (f_y + b~_y)^2
+        thr = alpha1 * ((f_x^2 + f_y^2) + (b~_x^2 + b~_y^2)) + alpha2
+        visible iff in frame, r2 and thr finite, r2 <= thr
+
+    Returns (occ_fw, occ_bw, res_fw, res_bw, stats):
+        occ   uint8 (N,1,H,W), 1 where not visible
+        res   fp32 (N,1,H,W), sqrt(r2); +inf out of frame or non-finite
+        stats fp64 (N,2,4), per sample and direction (0 = fw, 1 = bw):
+              visible count, in-frame-but-inconsistent count,
+              out-of-frame-or-non-finite count, sum of sqrt(r2) over visible
+    return_margin: also return the smallest |r2 - thr| over the finite
+    in-frame pixels of both directions (inf when there is none): how far the
+    closest decision sits from its threshold.
+    """
+    if (flow_fw.dim() != 4 or flow_fw.shape[1] != 2
+            or flow_fw.shape != flow_bw.shape
+            or flow_fw.shape[2] < 2 or flow_fw.shape[3] < 2):
+        raise ValueError(
+            "fb_consistency: two (N,2,H,W) flows of one shape, H, W >= 2; got "
+            f"{tuple(flow_fw.shape)} and {tuple(flow_bw.shape)}")
+    f = flow_fw.detach().double()
+    b = flow_bw.detach().double()
+    occ_fw, res_fw, st_fw, gap_fw = _fb_one_direction(f, b, alpha1, alpha2)
+    occ_bw, res_bw, st_bw, gap_bw = _fb_one_direction(b, f, alpha1, alpha2)
+    out = (occ_fw, occ_bw, res_fw, res_bw, torch.stack([st_fw, st_bw], dim=1))
+    if return_margin:
+        return out + (torch.minimum(gap_fw, gap_bw),)
+    return out
 
 
 # ---------------------------------------------------------------------------

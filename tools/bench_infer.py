@@ -5,7 +5,7 @@ pairs/sec as JSON lines.
 
     python tools/bench_infer.py [--iters 24] [--height 288] [--width 960]
                                 [--alternate_corr] [--reps 20] [--no_eager]
-                                [--warm_start]
+                                [--warm_start] [--bidirectional]
 
 Every line also carries `max_mem_mb` (torch.cuda.max_memory_allocated).
 
@@ -13,6 +13,13 @@ Every line also carries `max_mem_mb` (torch.cuda.max_memory_allocated).
 the previous pair's splatted flow: ms per frame with the host scipy splat,
 with the device splat run eagerly, and with the device splat inside the
 replayed graph (plus `max_abs_diff_vs_eager` between the two device routes).
+
+--bidirectional times both directions of one frame pair, each build in a
+fresh peak-memory window: two graphed unidirectional replays, (a,b) then
+(b,a); the graphed bidirectional replay (`ratio_vs_two_calls` against the
+former); the same with the consistency check in the graph (`added_ms`); and
+`ops.fb_consistency` alone on that `flow_up`, the HIP kernel against its
+float64 torch twin.
 """
 
 import argparse
@@ -111,6 +118,96 @@ def bench_warm_start(model, args, tag):
            max_abs_diff_vs_eager=err.item())
 
 
+def bench_bidirectional(model, args, tag):
+    """Both directions of one pair: two unidirectional replays against one
+    bidirectional replay, with and without the consistency check; then the
+    check alone, kernel against twin."""
+    from flowhip import ops
+    from flowhip.ops import torch_ref
+
+    dev = next(model.parameters()).device
+    shape = (args.batch, 3, args.height, args.width)
+    gen = torch.Generator().manual_seed(4321)
+    a = (torch.rand(shape, generator=gen) * 255).to(dev)
+    b = (torch.rand(shape, generator=gen) * 255).to(dev)
+
+    def report(probe, **fields):
+        print(json.dumps({"probe": probe, **fields,
+                          "max_mem_mb": torch.cuda.max_memory_allocated()
+                          / 2 ** 20, **tag}), flush=True)
+
+    def fresh():
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+
+    fresh()
+    g = GraphedInference(model, shape, args.iters)
+
+    def two_calls():
+        g(a, b)
+        g(b, a)
+    t_two = timeit(two_calls, iters=args.reps) * 1e3
+    up_fw = g(a, b)[1].clone()
+    up_bw = g(b, a)[1].clone()
+    report("two_unidirectional_hipgraph", ms=t_two)
+    del g
+
+    fresh()
+    g = GraphedInference(model, shape, args.iters, bidirectional=True)
+    t_bi = timeit(lambda: g(a, b), iters=args.reps) * 1e3
+    up = g(a, b)[1]
+    sep = torch.cat([up_fw, up_bw])
+    err = (up - sep).abs().max().item()
+    report("bidirectional_hipgraph", ms=t_bi,
+           ratio_vs_two_calls=t_bi / t_two, max_abs_diff_vs_two_calls=err,
+           max_abs_flow=sep.abs().max().item())
+    del g, up
+
+    # the batch sensitivity the kernels have without this feature: the plain
+    # forward on the stacked pairs (eager, once) against the same two calls
+    fresh()
+    with torch.no_grad():
+        err0 = (model(torch.cat([a, b]), torch.cat([b, a]), iters=args.iters,
+                      test_mode=True)[1] - sep).abs().max().item()
+    report("stacked_unidirectional_eager", max_abs_diff_vs_two_calls=err0)
+    del sep
+
+    fresh()
+    g = GraphedInference(model, shape, args.iters, bidirectional=True,
+                         consistency=True)
+    t_chk = timeit(lambda: g(a, b), iters=args.reps) * 1e3
+    up = g(a, b)[1].clone()
+    stats = g.consistency[4].clone()
+    npix = args.height * args.width
+    report("bidirectional_consistency_hipgraph", ms=t_chk,
+           added_ms=t_chk - t_bi, ratio_vs_two_calls=t_chk / t_two,
+           visible_share=(stats[..., 0] / npix).flatten().tolist())
+    del g
+
+    # the check alone on that flow_up: variants interleaved in one process
+    fw, bw = up[:args.batch], up[args.batch:]
+    variants = {
+        "hip": lambda: ops.fb_consistency(fw, bw),
+        "torch_twin": lambda: torch_ref.fb_consistency(fw, bw),
+    }
+    times = {k: [] for k in variants}
+    for fn in variants.values():
+        timeit(fn, warmup=2, iters=2)
+    for _ in range(5):
+        for k, fn in variants.items():
+            times[k].append(timeit(fn, warmup=0, iters=10) * 1e3)
+    got, ref = variants["hip"](), variants["torch_twin"]()
+    fresh()
+    report("fb_consistency_alone",
+           **{k + "_ms_median": sorted(v)[len(v) // 2]
+              for k, v in times.items()},
+           **{k + "_ms_min": min(v) for k, v in times.items()},
+           occ_mismatches=int((got[0] != ref[0]).sum()
+                              + (got[1] != ref[1]).sum()),
+           counts_equal=bool(torch.equal(got[4][..., :3], ref[4][..., :3])))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=24)
@@ -126,6 +223,10 @@ def main():
     ap.add_argument("--warm_start", action="store_true",
                     help="time warm-started sequence inference per frame: "
                     "host scipy splat, eager device splat, splat in the graph")
+    ap.add_argument("--bidirectional", action="store_true",
+                    help="time both directions of a pair: one bidirectional "
+                    "replay (with and without the consistency check) against "
+                    "two unidirectional replays; the check against its twin")
     args = ap.parse_args()
 
     dev = torch.device("cuda:0")
@@ -145,6 +246,9 @@ def main():
            "hw": [args.height, args.width], "batch": args.batch}
     if args.warm_start:
         bench_warm_start(model, args, tag)
+        return
+    if args.bidirectional:
+        bench_bidirectional(model, args, tag)
         return
     t_eager = None
     if not args.no_eager:
